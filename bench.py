@@ -7,11 +7,17 @@ predict + update (+ applyDelta) pass over the whole batch = B filter steps.
 `--filter usckf` runs the batched Usckf step instead (N = 48, m = 3: BASELINE configs[0]/[1]'s shape).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--clones k] [--meas m] [--filter msckf|usckf]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one child process per GPU,
 started before this process touches torch, HIP or the product library) and relays rank 0's line.
 Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR` writes, after the timed steps, what rank 0's batch holds after the last one -- what a caller of
+the step receives: mean.npy [S, Nq], P.npy [S, N, N], status.npy [S], outliers.npy [S] (float64) for a fixed seeded
+sample of S filters whose indices are filter_index.npy (all filters when they fit in DUMP_BUDGET bytes).  The inputs
+depend on the arguments only, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -30,6 +36,8 @@ PEAK_FP64_MFMA_TFLOPS = 78.6   # MI355X fp64 matrix peak (public spec; BASELINE.
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 SEED0 = 0x5EED0000             # rank r owns the filters seeded SEED0 + r
 ST_ALL_REJECTED = 8            # include/slk.h SLK_ST_ALL_REJECTED: every measurement block failed the gate (not an error)
+DUMP_BUDGET = 60 * 2 ** 20     # --dump-outputs writes at most this many bytes (under 64 MB)
+DUMP_SAMPLE_SEED = 0x5EED0D00  # --dump-outputs: the filter sample of a batch too large for DUMP_BUDGET
 
 
 def algorithmic_flops(N, m, msckf=True):
@@ -205,6 +213,9 @@ class Rehearsal:
         st[self.rank:3 * self.rank] = ST_ALL_REJECTED  # 2r filters whose blocks were all gated out
         return st
 
+    def outputs(self):
+        return {"status": self.status()}
+
 
 class GpuBatch:
     """The filter batch of one rank on its MI355X: the product library behind the reference's filter interface
@@ -271,6 +282,29 @@ class GpuBatch:
     def status(self):
         return self.f.status()
 
+    def outputs(self):
+        """The state a caller of the step receives (Msckf: muState, getPk; Usckf: muState, PkAugmentedState), with the
+        per-filter status words and outlier masks."""
+        f = self.f
+        P = f.PkAugmentedState() if self.kind == "usckf" else f.getPk()
+        return {"mean": f.muState(), "P": P, "status": f.status(), "outliers": f.outliers()}
+
+
+def dump_outputs(path, outputs, budget=DUMP_BUDGET, seed=DUMP_SAMPLE_SEED):
+    """--dump-outputs: each per-filter array of `outputs` as <path>/<name>.npy in float64 (status words and outlier
+    masks are exact in it), restricted to one sample of filters so that all files together stay within `budget` bytes,
+    and the sample's indices as filter_index.npy."""
+    import numpy as np
+    arrs = {n: np.asarray(a) for n, a in outputs.items()}
+    B = len(next(iter(arrs.values())))
+    per_filter = 8 * (1 + sum(a[0].size for a in arrs.values()))
+    S = min(B, budget // per_filter)
+    idx = np.arange(B) if S == B else np.sort(np.random.default_rng(seed).choice(B, S, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "filter_index.npy"), idx.astype(np.float64))
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a[idx], dtype=np.float64))
+
 
 def make_workload(args, rank, local_rank):
     """The one place where the bench meets the product library (tests replace the filter batch here)."""
@@ -311,6 +345,8 @@ def run_rank(args, rank, local_rank, world, factory=make_workload):
     elapsed = time.perf_counter() - t0
 
     status = np.asarray(w.status())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w.outputs())
     numerical = status & ~ST_ALL_REJECTED
     mine = [args.steps, int(elapsed * 1e9), int(kernel_ms_total * 1e6), int(np.bitwise_or.reduce(status)) if status.size else 0,
             int(np.count_nonzero(numerical)), int(np.count_nonzero(status & ST_ALL_REJECTED)), w.seed, w.B]
@@ -445,6 +481,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launch/rendezvous/gather path (gloo, no GPU, no kernels); "
                          "its numbers are meaningless and marked as such")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's filter outputs of the last step as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -453,6 +491,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(launch_ranks(args.gpus, argv))          # nothing GPU-related has been imported or called yet

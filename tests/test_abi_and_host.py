@@ -140,6 +140,7 @@ def test_bench_rejects_a_launcher_with_another_world_size():
 
 def test_bench_failing_rank_fails_the_run():
     # a rank that dies (here: no GPU for the real workload) must take the run down with a non-zero status, not hang
+    import torch  # noqa: F401  (before the library, so that both use one HIP runtime: see __graft_entry__.build)
     from slkpkg import slk as mod
     if mod.device_count() > 0:
         pytest.skip("a GPU is visible")
