@@ -22,7 +22,7 @@
 
 // The largest step-kernel instantiations are compiled in translation units of their own (slk_inst_big.hip,
 // slk_inst_mid.hip) so that the library's build runs them in parallel; development builds (one file) keep none of them.
-#if !defined(SLK_DEV_N60) && !defined(SLK_ONE_TU)
+#ifndef SLK_DEV_N60
 namespace slk {
 extern template __global__ void msckf_step_kernel<13, 512, -1, 0>(KArgs);
 extern template __global__ void msckf_step_kernel<13, 512, 31, 8>(KArgs);
@@ -272,9 +272,8 @@ static int launch_msckf_inst(slk_filter *f, const KArgs &a0)
                 a.lower_only = 1;
                 f->upper_stale = true;
             }
-#ifndef SLK_MSCKF_FACTOR_KERNEL      // the first factorisation inside the update kernel's fast path: two launches per step, no factor round trip
+            // the first factorisation inside the update kernel's fast path: two launches per step, no factor round trip
             if (a.do_update && a.emit == 0 && a.mm == SLK_MM_FEATURE_PROJ && a.m == 8 && a.gate != 2 && a.rebuild_prec == 0 && a.mp) a.wsfail = nullptr;
-#endif
         }
         auto kern = msckf_step_kernel<NT, NTHREADS, KST, MST>;
         rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), f->cfg.device, lds);
@@ -379,19 +378,14 @@ static int launch_msckf(slk_filter *f, const KArgs &a0)
         a.do_predict = 0;                       // the step kernel takes the predicted state from memory
     }
 #ifdef SLK_DEV_N60      // development builds (tools/ab.sh): only the headline instantiations, for quick A/B turnarounds
-#ifdef SLK_DEV_SMALL    // (-DSLK_DEV_SMALL: only BASELINE config 2's exact shapes, N = 12 / m = 3 and N = 18 / m = 2)
-    if (NT == 1 && a.lay.k == 0 && a.m == 3) return launch_msckf_inst<1, 64, 0, 3>(f, a);
-    if (NT == 2 && a.lay.k == 1 && a.m == 2) return launch_msckf_inst<2, 64, 1, 2>(f, a);
-#elif !defined(SLK_DEV_EKF)     // (-DSLK_DEV_EKF: only the EKF tile kernel)
     if (NT == 4) return launch_msckf_n60(f, a);
-#endif
     g_err = "development build: N = 49..64 only"; return SLK_E_UNSUPPORTED;
 #else
     switch (NT) {
-    case 1: {                                   // N = 12 (BASELINE config 2): exact shape, with m = 3 rows exact offsets too
+    case 1: {                                   // N = 12 (k = 0, BASELINE config 2): exact shape, with m = 3 rows exact offsets too
         const bool mx = a.do_update && a.emit == 0 && a.rebuild_prec == 0;
-        if (a.lay.k == 0 && a.m == 3 && mx) return launch_msckf_inst<1, 64, 0, 3>(f, a);
-        return (a.lay.k == 0) ? launch_msckf_inst<1, 64, 0>(f, a) : launch_msckf_inst<1, 64>(f, a);
+        if (a.m == 3 && mx) return launch_msckf_inst<1, 64, 0, 3>(f, a);
+        return launch_msckf_inst<1, 64, 0>(f, a);
     }
     case 2: {                                   // N = 18
         const bool mx = a.do_update && a.emit == 0 && a.rebuild_prec == 0;
@@ -427,23 +421,25 @@ static int launch_usckf_inst(slk_filter *f, const KArgs &a)
     return SLK_OK;
 }
 
-// N <= 64, plain predict / update / step calls: three launches per step (predict and factorisation as one wave per filter,
-// the update with the covariance left in global memory) -- the fused kernel above keeps the Tier-B modes and N > 64.
-template <int NT>
+#ifndef SLK_DEV_N60
+// N <= 48 (NT = 3), plain predict / update / step calls: three launches per step (predict and factorisation as one wave per
+// filter, the update with the covariance left in global memory) -- the fused kernel above keeps the Tier-B modes and N > 48.
 static int launch_usckf_split(slk_filter *f, const KArgs &a0)
 {
     KArgs a = a0;
+    // the unit-test shape (UsckfUnitTest.cpp: 3 + 9 features, N = 48, m = 3 rows)
+    const bool unit_shape = a.lay.nfk == 3 && a.lay.nfkl == 9;
     // The unit-test shape keeps the lower triangle (and the diagonal 16 x 16 tiles) of the covariance up to date only:
     // predict, the factorisation and the exact-shape update read nothing else (Usckf.hpp:537: Eigen::LLT); the strict upper
-    // triangle is completed before anything else sees the matrix (mirror_upper).  -DSLK_USCKF_FULL_P: both triangles, always.
-#ifndef SLK_USCKF_FULL_P
-    if (NT == 3 && a.lay.N == 48 && a.lay.nfk == 3 && a.lay.nfkl == 9 && a.emit == 0 && !a.P_out && a.P == f->d_P
+    // triangle is completed before anything else sees the matrix (mirror_upper).  Against both triangles, always:
+    // 0.0904 -> 0.0832 ms per step, HBM traffic 384 -> 176 MB per step.
+    if (unit_shape && a.emit == 0 && !a.P_out && a.P == f->d_P
         && (!a.do_update || (a.m == 3 && a.mm == SLK_MM_VO_RELATIVE && a.gate <= 9))) {
         a.lower_only = 1;
         f->upper_stale = true;
-    } else
-#endif
-    { int rcm = mirror_upper(f); if (rcm) return rcm; }
+    } else {
+        int rcm = mirror_upper(f); if (rcm) return rcm;
+    }
     if (a.do_predict) {
         hipLaunchKernelGGL(usckf_predict_kernel, dim3(a.B), dim3(64), 0, f->stream, a);
         HIPCHECK(hipGetLastError());
@@ -451,12 +447,8 @@ static int launch_usckf_split(slk_filter *f, const KArgs &a0)
         a.do_predict = 0;
     }
     // the exact shape with the plain update factors inside the update kernel (slk_usckf_fast.hpp): two launches per step,
-    // no factor round trip through memory (-DSLK_USCKF_FACTOR_KERNEL: the three-launch form, for A/B runs)
-    bool fused_factor = false;
-#ifndef SLK_USCKF_FACTOR_KERNEL
-    if constexpr (NT == 3)
-        fused_factor = a.lay.nfk == 3 && a.lay.nfkl == 9 && a.m == 3 && a.emit == 0 && a.mm == SLK_MM_VO_RELATIVE && a.gate <= 9;
-#endif
+    // no factor round trip through memory (against the factor kernel: 0.0946 -> 0.0916 ms per step)
+    const bool fused_factor = unit_shape && a.m == 3 && a.emit == 0 && a.mm == SLK_MM_VO_RELATIVE && a.gate <= 9;
     int rc = SLK_OK;
     if (fused_factor) {
         a.wsL = nullptr;
@@ -468,46 +460,45 @@ static int launch_usckf_split(slk_filter *f, const KArgs &a0)
         if (rc) return rc;
         a.wsL = f->ws_L.p;
         a.wsfail = reinterpret_cast<int *>(f->ws_DR.p);
-        if (NT == 3 && a.lay.N == 48) {             // the unit-test shape: the exact-size factor kernel (same N as 6 Msckf clones)
+        if (a.lay.N == 48) {                        // the unit-test shape: the exact-size factor kernel (same N as 6 Msckf clones)
             hipLaunchKernelGGL((msckf_chol_kernel<3, 6>), dim3(a.B), dim3(64), 0, f->stream, a);
         } else {
-            hipLaunchKernelGGL((msckf_chol_kernel<NT, -1>), dim3(a.B), dim3(64), 0, f->stream, a);
+            hipLaunchKernelGGL((msckf_chol_kernel<3, -1>), dim3(a.B), dim3(64), 0, f->stream, a);
         }
         HIPCHECK(hipGetLastError());
     }
-    UCarve cv = carve_usckf(a.lay.N, a.lay.Nq, a.m, NT, true);
+    UCarve cv = carve_usckf(a.lay.N, a.lay.Nq, a.m, 3, true);
     const size_t lds = (size_t)cv.total * sizeof(double);
-#ifndef SLK_USCKF_UPD_THREADS
-#define SLK_USCKF_UPD_THREADS 128   // two waves per filter: twice the filters in flight, fewer barrier waits (A/B: 256 -> 188 us, 128 -> 165 us, 64 -> 172 us at B = 4096)
-#endif
-    auto kern = usckf_kernel<NT, SLK_USCKF_UPD_THREADS, true>;
+    // two waves per filter: twice the filters in flight, fewer barrier waits (A/B: 256 -> 188 us, 128 -> 165 us, 64 -> 172 us
+    // at B = 4096)
+    constexpr int UPD_THREADS = 128;
+    auto kern = usckf_kernel<3, UPD_THREADS, true>;
     size_t lds_fast = 0;
-    if constexpr (NT == 3) {                    // the unit-test shape: exact instantiation (with its fast path's own LDS carve)
-        if (a.lay.nfk == 3 && a.lay.nfkl == 9 && a.m == 3) { kern = usckf_kernel<3, SLK_USCKF_UPD_THREADS, true, true>; lds_fast = (size_t)UFast::total * sizeof(double); }
+    if (unit_shape && a.m == 3) {               // the unit-test shape: exact instantiation (with its fast path's own LDS carve)
+        kern = usckf_kernel<3, UPD_THREADS, true, true>;
+        lds_fast = (size_t)UFast::total * sizeof(double);
     }
     const size_t lds_use = lds > lds_fast ? lds : lds_fast;
     rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), f->cfg.device, lds_use);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(SLK_USCKF_UPD_THREADS), lds_use, f->stream, a);
+    hipLaunchKernelGGL(kern, dim3(a.B), dim3(UPD_THREADS), lds_use, f->stream, a);
     HIPCHECK(hipGetLastError());
     return SLK_OK;
 }
+#endif
 
 static int launch_usckf(slk_filter *f, const KArgs &a)
 {
     int NT = (a.lay.N + 15) / 16;
     if (f->upper_stale && (a.emit != 0 || a.lay.N > 48)) { int rcm = mirror_upper(f); if (rcm) return rcm; }   // (the fused kernels stage the whole matrix)
-#if defined(SLK_DEV_N60) && defined(SLK_DEV_USCKF)       // (-DSLK_DEV_USCKF: the split path of N <= 48 only)
-    if (NT == 3 && a.emit == 0) return launch_usckf_split<3>(f, a);
-    g_err = "development build: Usckf split path of N <= 48 only"; return SLK_E_UNSUPPORTED;
-#elif defined(SLK_DEV_N60)
+#ifdef SLK_DEV_N60
     (void)NT; (void)f; (void)a;
     g_err = "development build: Msckf only"; return SLK_E_UNSUPPORTED;
 #else
     const bool split = a.emit == 0 && a.lay.N <= 48;       // (usckf_predict_kernel stages 12 x N old rows and Fk in its 736 doubles of scratch)
     switch (NT) {
-    case 3: return split ? launch_usckf_split<3>(f, a) : launch_usckf_inst<3>(f, a);
-    case 4: return split ? launch_usckf_split<4>(f, a) : launch_usckf_inst<4>(f, a);
+    case 3: return split ? launch_usckf_split(f, a) : launch_usckf_inst<3>(f, a);
+    case 4: return launch_usckf_inst<4>(f, a);
     case 5: return launch_usckf_inst<5>(f, a);
     case 6: return launch_usckf_inst<6>(f, a);
     default: g_err = "Usckf state dimension above 96 is not supported by this build"; return SLK_E_UNSUPPORTED;
@@ -837,7 +828,7 @@ int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const do
 #ifdef SLK_STAMPS
     a.dbg = g_dbg;
 #endif
-#if defined(SLK_DEV_N60) && !defined(SLK_DEV_EKF)
+#ifdef SLK_DEV_N60
     g_err = "development build: no EKF kernels"; return SLK_E_UNSUPPORTED;
 #else
     const size_t lds = ekf_tile_lds_doubles(N, m) * sizeof(double);
@@ -847,11 +838,7 @@ int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const do
         if (rc) return rc;
         hipLaunchKernelGGL(kern, dim3(f->B), dim3(1024), lds, f->stream, a);
     } else {
-#ifdef SLK_DEV_EKF
-        g_err = "development build: EKF tile kernel only"; return SLK_E_UNSUPPORTED;
-#else
         hipLaunchKernelGGL(msckf_ekf_kernel<256>, dim3(f->B), dim3(256), 0, f->stream, a);
-#endif
     }
     HIPCHECK(hipGetLastError());
     return SLK_OK;

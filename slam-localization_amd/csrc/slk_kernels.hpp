@@ -18,9 +18,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 
 constexpr int KP = 8;        // sigma points per rebuild panel (2 MFMA k-steps), double-buffered
-#ifndef SLK_WGS
-#define SLK_WGS 4     // workgroups per CU the N <= 64 kernels are built for (register budget 512 / SLK_WGS)
-#endif
+constexpr int STEP_WGS = 4;  // workgroups per CU the N <= 64 kernels are built for (register budget 512 / STEP_WGS)
 constexpr int MAXM = 32;     // max measurement rows handled on chip
 constexpr int PRED_SCRATCH = 1536;  // doubles of pool used by the 12-DOF predict phase
 
@@ -1976,19 +1974,14 @@ template <int NT, int NTHREADS, int KST, int MST> struct HasFastStep {
 template <int NT, int NTHREADS, int KST = -1, int MST = 0>
 // (register budget: the exact-shape instantiations (k and m known) fit 128 registers = four workgroups per CU; the run-time
 // shapes of N = 33 .. 64 need more live index arithmetic and get 256 = two workgroups per CU instead of scratch memory)
-__global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? (MST > 0 ? SLK_WGS : 2) : ((NT >= 5 && NT <= 8) ? 2 : (NT <= 2 ? 4 : 1)))) void msckf_step_kernel(KArgs a)
+__global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? (MST > 0 ? STEP_WGS : 2) : ((NT >= 5 && NT <= 8) ? 2 : (NT <= 2 ? 4 : 1)))) void msckf_step_kernel(KArgs a)
 {
     constexpr bool BIG = NT > 4;                           // large state (N > 64): factor + rotation store in the global workspace
     extern __shared__ __attribute__((aligned(16))) double smem[];
-#ifndef SLK_NO_FAST_STEP
     if constexpr (HasFastStep<NT, NTHREADS, KST, MST>::value) {
         if (!a.do_predict && a.do_update && msckf_step_fast<KST>(a, smem)) return;
     }
-#endif
     constexpr int NW = NTHREADS / 64;
-    constexpr int GD = Grid<NTHREADS>::GD;
-    constexpr int SDN = (16 * NT + GD - 1) / GD;          // Cholesky register slots per dimension
-    constexpr int SDM = (MAXM + GD - 1) / GD;
     constexpr int NROWS = (NT <= 2 && KST >= 0) ? 12 + 6 * KST : 1;      // rows of the one-wave register Cholesky (exact shapes, N <= 32)
     static_assert(NT > 2 || NTHREADS == 64, "states of N <= 32 run one wave per filter");
     const int bidx = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2079,37 +2072,32 @@ __global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? 
     if (a.do_update || a.emit >= 2) {
         // ---- sigma points of the full state: Msckf.hpp:228-229 -> :400-431
         int fail;
-#ifndef SLK_MSCKF_FACTOR_KERNEL
-        constexpr bool FACTOR_INSIDE = true;
-#else
-        constexpr bool FACTOR_INSIDE = false;
-#endif
-        if (FACTOR_INSIDE && WCHOL && !a.wsfail) {
-            // no factor in the workspace (the exact-shape launch factors inside the fast path, and this body is its fallback):
-            // one wave, panel by rows, straight into LDS
-            if constexpr (WCHOL && FACTOR_INSIDE) {
+        if constexpr (WCHOL) {
+            if (!a.wsfail) {
+                // no factor in the workspace (the exact-shape launch factors inside the fast path, and this body is its
+                // fallback): one wave, panel by rows, straight into LDS
                 if (wave == 0) {
                     d4 acc[CholM<NT>::NTL];
                     cholm_load_t<NT>(acc, N, lane, Pin);
                     const int f0 = cholp_factor<NT, 0>(acc, Lp, N, colbuf, lane);
                     if (lane == 0) ish[45] = f0;
                 }
-            }
-            __syncthreads();
-            fail = ish[45];
-        } else if constexpr (WCHOL) {
-            // the factor comes from msckf_chol_kernel (its own launch, one wave per filter at twelve filters per CU),
-            // packed, through a workspace
-            const double *gL = a.wsL + (size_t)bidx * pk_size(N);
-            for (int e0 = 0; e0 < pk_size(N); e0 += 8 * NTHREADS) {         // eight loads in flight per thread
-                double v[8];
+                __syncthreads();
+                fail = ish[45];
+            } else {
+                // the factor comes from msckf_chol_kernel (its own launch, one wave per filter at twelve filters per CU),
+                // packed, through a workspace
+                const double *gL = a.wsL + (size_t)bidx * pk_size(N);
+                for (int e0 = 0; e0 < pk_size(N); e0 += 8 * NTHREADS) {         // eight loads in flight per thread
+                    double v[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { const int e = e0 + q * NTHREADS + tid; v[q] = (e < pk_size(N)) ? gL[e] : 0.0; }
+                    for (int q = 0; q < 8; ++q) { const int e = e0 + q * NTHREADS + tid; v[q] = (e < pk_size(N)) ? gL[e] : 0.0; }
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { const int e = e0 + q * NTHREADS + tid; if (e < pk_size(N)) Lp[e] = v[q]; }
+                    for (int q = 0; q < 8; ++q) { const int e = e0 + q * NTHREADS + tid; if (e < pk_size(N)) Lp[e] = v[q]; }
+                }
+                fail = a.wsfail[bidx];
+                __syncthreads();
             }
-            fail = a.wsfail[bidx];
-            __syncthreads();
         } else if constexpr (NT <= 2 && KST >= 0) {
             fail = chol_state([](int) { return 0.0; });                // (one wave per filter: no barrier)
         } else if constexpr (NT <= 4) {
@@ -2121,12 +2109,10 @@ __global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? 
             }
             __syncthreads();
             fail = ish[45];
-        } else if constexpr (BIG) {
-            // (the launcher ran msckf_chol_big_kernel: the factor is in the workspace already)
+        } else {
+            // (BIG: the launcher ran msckf_chol_big_kernel, the factor is in the workspace already)
             if (a.wsfail) fail = a.wsfail[bidx];
             else fail = chol_blocked_mem<NTHREADS>(Lp, N, pool, colbuf, &ish[45], tid, Pin);
-        } else {
-            fail = chol_packed<NTHREADS, SDN>(Lp, N, colbuf, tid, Pin);
         }
         SLK_STAMP(3);
         bool redraw = false;
@@ -2481,30 +2467,26 @@ __global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? 
                         __syncthreads();
                         fail = ish[45];
                     } else {
+                        // (BIG) applyDelta's factor as a factor UPDATE by tile rows (factor_update_blocks): O(N^2 m) instead
+                        // of the O(N^3) factorisation of the downdated matrix; needs covXZ = L A (no wrapped rotation
+                        // column), at most eight rows and an SPD innovation covariance.  The gain K (in Z's place) is
+                        // dead once delta stands: Z holds W and the wave totals, the Cholesky panel the M_JJ tiles.
                         auto down = [&](int i, int j) {
                             double p = Pin(i, j);
                             double sum = 0.0;
                             for (int c = 0; c < mmr; ++c) sum += Pxz[i + N * idx[c]] * K[j + N * c];
                             return p - sum;
                         };
-                        if constexpr (BIG) {
-                            double *panel = innov + 2 * round_up(m, 2);      // behind the measurement arrays
-                            // applyDelta's factor as a factor UPDATE by tile rows (factor_update_blocks): O(N^2 m) instead
-                            // of the O(N^3) factorisation of the downdated matrix; needs covXZ = L A (no wrapped rotation
-                            // column), at most eight rows and an SPD innovation covariance.  The gain K (in Z's place) is
-                            // dead once delta stands: Z holds W and the wave totals, the Cholesky panel the M_JJ tiles.
-                            if (m <= 8 && mmr <= 8 && sfail < 0 && ish[42] == 0) {
-                                unsigned kept = 0;
-                                for (int r = 0; r < mmr; ++r) kept |= 1u << idx[r];
-                                __syncthreads();
-                                const bool pd = factor_update_blocks<NTHREADS>(Lp, N, DZ, m, Sm, kept, Z, md, Z + round_up(8 * N, 2),
-                                                                               panel, &ish[44], tid);
-                                fail = pd ? -1 : 0;                          // not positive definite: as a failed LLT
-                            } else {
-                                fail = chol_blocked_mem<NTHREADS>(Lp, N, panel, colbuf, &ish[45], tid, down);
-                            }
+                        double *panel = innov + 2 * round_up(m, 2);      // behind the measurement arrays
+                        if (m <= 8 && mmr <= 8 && sfail < 0 && ish[42] == 0) {
+                            unsigned kept = 0;
+                            for (int r = 0; r < mmr; ++r) kept |= 1u << idx[r];
+                            __syncthreads();
+                            const bool pd = factor_update_blocks<NTHREADS>(Lp, N, DZ, m, Sm, kept, Z, md, Z + round_up(8 * N, 2),
+                                                                           panel, &ish[44], tid);
+                            fail = pd ? -1 : 0;                          // not positive definite: as a failed LLT
                         } else {
-                            fail = chol_packed<NTHREADS, SDN>(Lp, N, colbuf, tid, down);
+                            fail = chol_blocked_mem<NTHREADS>(Lp, N, panel, colbuf, &ish[45], tid, down);
                         }
                     }
                     SLK_STAMP(11);
@@ -3327,26 +3309,19 @@ __global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? 
 // filters (round 2, cholm_factor at 168 registers: 45.7 us; four waves per filter, two barriers per step: 68 us).
 // The exact shapes of the fast path (k = 4 .. 8 clones, eight rows) and the Usckf unit-test shape run the same
 // factorisation INSIDE their update kernels instead (no factor round trip through memory): this kernel serves the other
-// shapes of N <= 64 and the -DSLK_MSCKF_FACTOR_KERNEL / -DSLK_USCKF_FACTOR_KERNEL builds; -DSLK_CHOL_BY_TILES: round 2's form.
-#ifndef SLK_CHOL1_WAVES
-#define SLK_CHOL1_WAVES 3
-#endif
+// shapes of N <= 64.
+constexpr int CHOL1_WAVES = 3;      // waves per SIMD the factor kernel of N = 49 .. 64 is compiled for
 template <int NT, int KST = -1>
 // (N <= 48: six tiles in registers -- four waves per SIMD, sixteen filters per CU: 4096 filters are one round)
-__global__ __launch_bounds__(64, (NT <= 3 ? 4 : SLK_CHOL1_WAVES)) void msckf_chol_kernel(KArgs a)
+__global__ __launch_bounds__(64, (NT <= 3 ? 4 : CHOL1_WAVES)) void msckf_chol_kernel(KArgs a)
 {
     __shared__ __attribute__((aligned(16))) double colbuf[CholM<NT>::COLBUF];
     const int bidx = blockIdx.x, lane = threadIdx.x;
     const int N = (KST >= 0) ? 12 + 6 * KST : a.lay.N;
     const double *gP = a.P + (size_t)bidx * N * N;
     d4 acc[CholM<NT>::NTL];
-#ifdef SLK_CHOL_BY_TILES
-    cholm_load<NT>(acc, N, lane, [&](int i, int j) { return gP[i + (size_t)j * N]; });
-    const int fail = cholm_factor<NT>(acc, a.wsL + (size_t)bidx * pk_size(N), N, colbuf, lane);
-#else
     cholm_load_t<NT>(acc, N, lane, [&](int i, int j) { return gP[i + (size_t)j * N]; });
     const int fail = cholp_factor<NT>(acc, a.wsL + (size_t)bidx * pk_size(N), N, colbuf, lane);
-#endif
     if (lane == 0) a.wsfail[bidx] = fail;
 }
 
@@ -3374,10 +3349,8 @@ __host__ inline size_t chol_big_lds(int N) { return (size_t)(16 * ((N + 15) / 16
 // eight resident waves here against the single busy wave per four it had inside the fused step kernel.
 // Also the Tier-B halves: emit == 1 writes the 25 sigma points, pm == SLK_MODEL_EXTERNAL takes f(X) from Yext.
 #ifndef SLK_INST_UNIT     // (non-template kernels: defined in the main translation unit only)
-#ifndef SLK_PRED_WAVES
-#define SLK_PRED_WAVES 4     // waves per SIMD the predict kernel is compiled for
-#endif
-__global__ __launch_bounds__(64, SLK_PRED_WAVES) void msckf_predict_kernel(KArgs a)
+constexpr int PRED_WAVES = 4;     // waves per SIMD the predict kernel is compiled for
+__global__ __launch_bounds__(64, PRED_WAVES) void msckf_predict_kernel(KArgs a)
 {
     __shared__ __attribute__((aligned(16))) double sm[16 + 320 + 736];
     const int bidx = blockIdx.x, tid = threadIdx.x;

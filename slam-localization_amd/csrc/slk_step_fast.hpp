@@ -501,13 +501,10 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     // a rotation column that may exceed pi (Msckf.hpp:407-413: covXZ = L A would not hold) -- meet in one barrier
     int jmax = 0, bad;
     // the factor: from msckf_chol_kernel's workspace, or (a.wsfail == nullptr) factored HERE by wave 0 -- cholp_factor, panel
-    // by rows, straight into the tiles -- while the other waves fetch the small arrays
-#ifndef SLK_MSCKF_FACTOR_KERNEL     // (-DSLK_MSCKF_FACTOR_KERNEL: the three-launch form, the factor through the workspace only -- same step time,
-    const bool here = a.wsfail == nullptr;       //  1.28 x instead of 0.74 x the algorithmic bytes: profiles/r03_ab_msckf_factor_inside.log)
-#else
-    constexpr bool here = false;
-    if (!a.wsfail) return false;
-#endif
+    // by rows, straight into the tiles -- while the other waves fetch the small arrays (against the factor through the
+    // workspace for every step: same step time, 0.74 x instead of 1.28 x the algorithmic bytes,
+    // profiles/r03_ab_msckf_factor_inside.log)
+    const bool here = a.wsfail == nullptr;
     {
         const double *gL = here ? gP : a.wsL + (size_t)bidx * pk_size(N);
         const int t = lane, It = t >> 4;
@@ -781,9 +778,6 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     }
     __syncthreads();
     if (ints[48] | ints[49] | ints[50]) SLK_FBAIL(5);                      // indefinite downdate / non-SPD S / large rotation: the general body decides
-#ifdef SLK_EXP_A
-    return true;
-#endif
     SLK_FSTAMP(8);
 
     // ---- applyDelta's factor: L' = L chol(I - B B^T) (:262-263, :659-662)

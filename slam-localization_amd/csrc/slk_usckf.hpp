@@ -29,7 +29,7 @@ __host__ __device__ inline UCarve carve_usckf(int N, int Nq, int m, int NT, bool
     return c;
 }
 
-// SPLIT (N <= 64, three launches per step like the Msckf path): predict runs in usckf_predict_kernel, the factorisation in
+// SPLIT (N <= 48, three launches per step like the Msckf path): predict runs in usckf_predict_kernel, the factorisation in
 // msckf_chol_kernel (one wave per filter each), and this kernel is the update alone: the covariance stays in global
 // memory (its diagonal for the moments, the downdate as a read-modify-write), the factor comes from the workspace.
 // UEX: exact-shape instantiation of the unit-test layout (UsckfUnitTest.cpp: 3 + 9 features, N = 48, m = 3 rows): layout
@@ -41,7 +41,6 @@ __global__ __launch_bounds__(NTHREADS) void usckf_kernel(KArgs a)
     constexpr int NW = NTHREADS / 64;
     constexpr int GD = Grid<NTHREADS>::GD;
     constexpr int SDN = (16 * NT + GD - 1) / GD;
-    constexpr int SDM = (MAXM + GD - 1) / GD;
     const int bidx = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     Lay L = a.lay;
     if constexpr (UEX) { L.kind = SLK_USCKF; L.nfk = 3; L.nfkl = 9; L.N = 48; L.Nq = 51; L.nso3 = 3; a.m = 3; }
@@ -53,11 +52,9 @@ __global__ __launch_bounds__(NTHREADS) void usckf_kernel(KArgs a)
     double *P = SPLIT ? gP : smem + cv.P, *Lm = smem + cv.Lm, *mu = smem + cv.mu, *colbuf = smem + cv.colbuf, *pool = smem + cv.pool;
     int *ish = reinterpret_cast<int *>(smem + cv.small);
     int status = 0;
-#ifndef SLK_NO_FAST_STEP
     if constexpr (SPLIT && UEX && NTHREADS == 128) {
         if (usckf_update_fast(a, smem)) return;                 // (slk_usckf_fast.hpp; false: before any global write)
     }
-#endif
     if (a.do_update && a.emit != 4 && tid == 0) a.outliers[bidx] = 0u;
     if (tid == 0) ish[42] = 0;
 
@@ -136,30 +133,30 @@ __global__ __launch_bounds__(NTHREADS) void usckf_kernel(KArgs a)
     if (a.do_update || a.emit == 2) {
         // ---- Usckf::update, Usckf.hpp:246-308
         int fail;
-        if (SPLIT && NT <= 4 && !a.wsfail) {
-            // no factor in the workspace (the exact-shape launch factors inside the update kernel, slk_usckf_fast.hpp, and
-            // this body is its fallback): one wave, panel by rows, straight into LDS
-            if constexpr (NT <= 4) {
+        if constexpr (SPLIT) {
+            if (!a.wsfail) {
+                // no factor in the workspace (the exact-shape launch factors inside the update kernel, slk_usckf_fast.hpp,
+                // and this body is its fallback): one wave, panel by rows, straight into LDS
                 if (wave == 0) {
                     d4 acc[CholM<NT>::NTL];
                     cholm_load_t<NT>(acc, N, lane, [&](int i, int j) { return gP[i + (size_t)j * N]; });
                     const int f0 = cholp_factor<NT, 0>(acc, Lm, N, colbuf, lane);
                     if (lane == 0) ish[45] = f0;
                 }
-            }
-            __syncthreads();
-            fail = ish[45];
-        } else if constexpr (SPLIT) {
-            const double *gL = a.wsL + (size_t)bidx * pk_size(N);
-            for (int e0 = 0; e0 < pk_size(N); e0 += 12 * NTHREADS) {      // twelve loads in flight per thread
-                double v[12];
+                __syncthreads();
+                fail = ish[45];
+            } else {
+                const double *gL = a.wsL + (size_t)bidx * pk_size(N);
+                for (int e0 = 0; e0 < pk_size(N); e0 += 12 * NTHREADS) {      // twelve loads in flight per thread
+                    double v[12];
 #pragma unroll
-                for (int q = 0; q < 12; ++q) { const int e = e0 + q * NTHREADS + tid; v[q] = (e < pk_size(N)) ? gL[e] : 0.0; }
+                    for (int q = 0; q < 12; ++q) { const int e = e0 + q * NTHREADS + tid; v[q] = (e < pk_size(N)) ? gL[e] : 0.0; }
 #pragma unroll
-                for (int q = 0; q < 12; ++q) { const int e = e0 + q * NTHREADS + tid; if (e < pk_size(N)) Lm[e] = v[q]; }
+                    for (int q = 0; q < 12; ++q) { const int e = e0 + q * NTHREADS + tid; if (e < pk_size(N)) Lm[e] = v[q]; }
+                }
+                fail = a.wsfail[bidx];
+                __syncthreads();
             }
-            fail = a.wsfail[bidx];
-            __syncthreads();
         } else if constexpr (NT <= 4) {
             if (wave == 0) {
                 d4 acc[CholM<NT>::NTL];
@@ -335,10 +332,8 @@ __global__ __launch_bounds__(NTHREADS) void usckf_kernel(KArgs a)
 // 12-DOF prediction of state k+i (predict_phase), Fk = Pxy^T Pk_i^-1 (:154), then the cross blocks: rows of state k+i
 // against everything else Fk * block (:200-208, :221-232), columns against statek / statek_l block * Fk^T (:190-198),
 // feature rows as transposes (:227, :235).  All old values are staged in LDS before the first write.
-#ifndef SLK_UPRED_WAVES
-#define SLK_UPRED_WAVES 4
-#endif
-__global__ __launch_bounds__(64, SLK_UPRED_WAVES) void usckf_predict_kernel(KArgs a)
+constexpr int UPRED_WAVES = 4;      // waves per SIMD the split predict kernel is compiled for
+__global__ __launch_bounds__(64, UPRED_WAVES) void usckf_predict_kernel(KArgs a)
 {
     // 9.9 KB and 128 registers: sixteen filters per CU, 4096 filters are ONE round (round 2: 13.4 KB, 190 registers, eight
     // filters per CU, two rounds of the same dependent chain).  Fk and the old rows RB live in the predict scratch (dead
