@@ -204,3 +204,51 @@ def synthetic_pose_ops(B=24, seed=0xD0E5):
     return dict(B=B, t2=t2, t1=t1, cov2=spd(6, 0.05, B), cov1=spd(6, 0.03, B), u=u, velcov=spd(6, 0.1, 1)[0], prev=prev,
                 n=n, steps=steps, xk=xk, Pk=spd(n, 0.02, B), z=z, H=H, R=spd(3, 0.02, 1)[0],
                 m1=5, m2=3, gamma=0.002, r2count=0)
+
+
+def dense_noise(n, B=None, scale=0.01, seed=0xD0153):
+    """Dense, correlated SPD noise covariance(s): A A^T + eps I normalised to a correlation matrix (off-diagonal terms of
+    order 0.3), then scaled to variances spread 10:1 around `scale` (permuted per matrix).  B = None: one shared [n, n]
+    matrix, else per-filter [B, n, n]."""
+    rng = np.random.default_rng(seed)
+    cnt = 1 if B is None else B
+    A = rng.normal(0, 1, (cnt, n, n))
+    M = A @ np.transpose(A, (0, 2, 1)) / n + 0.05 * np.eye(n)
+    d = np.sqrt(np.einsum("bii->bi", M))
+    C = M / (d[:, :, None] * d[:, None, :])
+    var = scale * np.array([rng.permutation(np.logspace(-0.5, 0.5, n)) for _ in range(cnt)])
+    s = np.sqrt(var)
+    out = C * (s[:, :, None] * s[:, None, :])
+    out = 0.5 * (out + np.transpose(out, (0, 2, 1)))
+    return np.ascontiguousarray(out[0] if B is None else out)
+
+
+def msckf_features(mean, k, nf, rng, meas_sigma=0.02):
+    """nf 2-D features for Msckf filters in state `mean` [B, 13+7k]: observing poses round-robin over 0..k (0 = statek,
+    c >= 1 = clone c-1), landmarks placed in front of them -> (feat [B, nf, 4], z [B, 2 nf])."""
+    B = mean.shape[0]
+    feat = np.zeros((B, nf, 4))
+    z = np.zeros((B, 2 * nf))
+    for j in range(nf):
+        c = (k - j) % (k + 1)                         # the newest clone first
+        s = 0 if c == 0 else 13 + 7 * (c - 1)
+        local = np.concatenate([rng.uniform(-1, 1, (B, 2)), rng.uniform(4, 8, (B, 1))], axis=1)
+        feat[:, j, 0:3] = mean[:, s:s + 3] + quat_rotate(mean[:, s + 3:s + 7], local)
+        feat[:, j, 3] = c
+        z[:, 2 * j:2 * j + 2] = local[:, 0:2] / local[:, 2:3] + rng.normal(0, meas_sigma, (B, 2))
+    return np.ascontiguousarray(feat), np.ascontiguousarray(z)
+
+
+def usckf_features(mean, poses=(0, 2), seed=0xFEA7):
+    """Features seen from the given poses of the Usckf layout (0 = statek, 1 = statek_l, 2 = statek_i) of filters in
+    state `mean` [B, 39+nfk+nfkl] -> (feat [B, len(poses), 4], z [B, 2 len(poses)])."""
+    rng = np.random.default_rng(seed)
+    B = mean.shape[0]
+    feat = np.zeros((B, len(poses), 4))
+    z = np.zeros((B, 2 * len(poses)))
+    for j, c in enumerate(poses):
+        local = np.concatenate([rng.uniform(-0.5, 0.5, (B, 2)), rng.uniform(4, 6, (B, 1))], axis=1)
+        feat[:, j, 0:3] = mean[:, 13 * c:13 * c + 3] + quat_rotate(mean[:, 13 * c + 3:13 * c + 7], local)
+        feat[:, j, 3] = c
+        z[:, 2 * j:2 * j + 2] = local[:, 0:2] / local[:, 2:3] + rng.normal(0, 0.02, (B, 2))
+    return np.ascontiguousarray(feat), np.ascontiguousarray(z)
