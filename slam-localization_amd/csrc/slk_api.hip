@@ -487,6 +487,28 @@ static int launch_usckf_split(slk_filter *f, const KArgs &a0)
 }
 #endif
 
+// N > 96: any state size, everything N-sized in a global workspace (slk_usckf_general.hpp).  Predict (or its Tier-B
+// emission) and update are launches of their own: a step is two.
+static int launch_usckf_general(slk_filter *f, const KArgs &a0)
+{
+    KArgs a = a0;
+    const bool upd = a.do_update || a.emit == 2 || a.emit == 4;
+    if (a.do_predict || a.emit == 1) {
+        hipLaunchKernelGGL(usckf_predict_general_kernel, dim3(a.B), dim3(64), 0, f->stream, a);
+        HIPCHECK(hipGetLastError());
+        if (a.emit == 1 || !upd) return SLK_OK;
+        a.do_predict = 0;
+    }
+    if (!upd) return SLK_OK;
+    const GenWs w = general_ws(a.lay.N, a.lay.Nq, 3, a.m > 0 ? a.m : 1, true);
+    int rc = stage_reserve(f, f->ws_L, (size_t)a.B * w.total);
+    if (rc) return rc;
+    a.wsL = f->ws_L.p;
+    hipLaunchKernelGGL(usckf_update_general_kernel, dim3(a.B), dim3(256), 0, f->stream, a);
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+}
+
 static int launch_usckf(slk_filter *f, const KArgs &a)
 {
     int NT = (a.lay.N + 15) / 16;
@@ -501,7 +523,7 @@ static int launch_usckf(slk_filter *f, const KArgs &a)
     case 4: return launch_usckf_inst<4>(f, a);
     case 5: return launch_usckf_inst<5>(f, a);
     case 6: return launch_usckf_inst<6>(f, a);
-    default: g_err = "Usckf state dimension above 96 is not supported by this build"; return SLK_E_UNSUPPORTED;
+    default: return launch_usckf_general(f, a);      // N > 96: any state size, everything in a global workspace
     }
 #endif
 }
@@ -1093,7 +1115,6 @@ int slk_usckf_set_measurement(slk_filter *f, int mode, const double *z, int n, c
     Lay oldL = f->lay;
     int nfk = mode == SLK_STATEK ? n : oldL.nfk, nfkl = mode == SLK_STATEK_L ? n : oldL.nfkl;
     Lay newL = make_lay(SLK_USCKF, 0, nfk, nfkl);
-    if (newL.N > 96) { g_err = "Usckf state dimension above 96 is not supported by this build"; return SLK_E_UNSUPPORTED; }
     size_t B = (size_t)f->B;
     const double *dz, *dR;
     int rc = stage_in(f, f->st_z, z, B * n, where, &dz);

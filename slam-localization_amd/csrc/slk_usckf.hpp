@@ -516,3 +516,4 @@ __global__ void usckf_set_measurement_kernel(const double *mean, const double *P
 } // namespace slk
 
 #include "slk_usckf_fast.hpp"
+#include "slk_usckf_general.hpp"

@@ -1,4 +1,8 @@
-"""Throughput of the batched Usckf path (BASELINE config 1 shape: N = 48, m = 3, SPD variant)."""
+"""Throughput of the batched Usckf path (BASELINE config 1 shape: N = 48, m = 3, SPD variant).
+
+usage: python tools/bench_usckf.py [--nfk A] [--nfkl B] [batch ...]   (default 3 + 9 features: N = 48, m = 3; the
+state is N = 36 + A + B and the update has m = A rows, MM_VO_RELATIVE -- N > 96 runs on the global-workspace path)"""
+import argparse
 import os
 import sys
 import time
@@ -15,10 +19,16 @@ def main():
     from slkpkg import slk
     import scenarios as sc
     from oracle import oracle as o
-    batches = [int(x) for x in sys.argv[1:]] or [1024, 4096, 16384]
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nfk", type=int, default=3)
+    ap.add_argument("--nfkl", type=int, default=9)
+    ap.add_argument("batches", type=int, nargs="*")
+    args = ap.parse_args()
+    nfk, nfkl, N = args.nfk, args.nfkl, 36 + args.nfk + args.nfkl
+    batches = args.batches or [1024, 4096, 16384]
     for B in batches:
-        s = sc.synthetic_usckf(B)
-        f = slk.Usckf(mean=s["mean"], P=s["P"], nfk=3, nfkl=9)
+        s = sc.synthetic_usckf(B, nfk=nfk, nfkl=nfkl)
+        f = slk.Usckf(mean=s["mean"], P=s["P"], nfk=nfk, nfkl=nfkl)
         dev = torch.device("cuda")
         u = torch.from_numpy(s["u"]).to(dev)
         z = torch.from_numpy(s["z"]).to(dev)
@@ -33,12 +43,12 @@ def main():
             f.step(slk.PM_CONST_VELOCITY, u, Q, z, slk.MM_VO_RELATIVE, None, R)
         ms = f.timer_stop() / K
         bad = int(np.count_nonzero(f.status()))
-        print(f"Usckf N=48 m=3 B={B}: {B / ms * 1e3:.3e} filter-steps/s, {ms:.4f} ms/step, filters with status {bad}")
-    s = sc.synthetic_usckf(64)
+        print(f"Usckf N={N} m={nfk} B={B}: {B / ms * 1e3:.3e} filter-steps/s, {ms:.4f} ms/step, filters with status {bad}")
+    s = sc.synthetic_usckf(64, nfk=nfk, nfkl=nfkl)
     t0 = time.perf_counter()
     n = 0
     for b in range(64):
-        g = o.Usckf(nfk=3, nfkl=9, mean=s["mean"][b], P=s["P"][b])
+        g = o.Usckf(nfk=nfk, nfkl=nfkl, mean=s["mean"][b], P=s["P"][b])
         uu = s["u"][b]
         pm = o.pm_const_velocity(uu[0:3], uu[3:6], uu[6])
         for _ in range(20):
