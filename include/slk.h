@@ -183,7 +183,13 @@ int  slk_adaptive_matrix(slk_adaptive *a, int n, const double *xk, const double 
  *      measurement arrays share one workgroup's LDS; a call whose carve exceeds 160 KiB is refused with
  *      SLK_E_UNSUPPORTED before any launch, the filter untouched (slk_step too).  At m = nfk (SLK_MM_VO_RELATIVE) that
  *      refuses e.g. N = 96 with nfk = 12, N = 90 with nfk = 18 and N = 80 with nfk = 24; m = 3 / 4 (pose position, two
- *      features) runs at every N <= 96. ---- */
+ *      features) runs at every N <= 96.
+ *      Measurement rows: Msckf m <= 32 (a wider call returns SLK_E_INVALID).  Usckf has no row limit: a call with
+ *      m > 32 (slk_update, slk_step, slk_update_from_sigma, slk_update_innovation) runs at every N on the wide update
+ *      (csrc/slk_usckf_wide.hpp: one workgroup per filter, the m-sized products on fp64 matrix cores); in slk_step the
+ *      predict takes its predict-only route first and the wide update is a launch of its own.  It reserves, per filter,
+ *      N(N+1)/2 + m(m+1)/2 + m^2 + 2Nm + (2N+1)m + 17 * (max(N, m) rounded up to 16) + 3m + 4N doubles (rounded up to 8),
+ *      kept by the handle between calls; a failed reservation returns before any launch. ---- */
 int slk_update(slk_filter *f, int model, const double *params, int p_stride,
                const double *z, int m, const double *R, int r_stride, int gate, int where);
 

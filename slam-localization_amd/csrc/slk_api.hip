@@ -509,6 +509,32 @@ static int launch_usckf_general(slk_filter *f, const KArgs &a0)
     return SLK_OK;
 }
 
+static int launch_usckf(slk_filter *f, const KArgs &a);
+
+// m > MAXM measurement rows, any N (slk_usckf_wide.hpp).  The workspace is reserved before anything is launched (a failed
+// reservation leaves the filter untouched).  The predict half of a step takes the route a predict-only call takes at this
+// N, then the update is a launch of its own: a step is bit-identical to predict followed by update.  The wide kernel reads
+// the lower triangle of P only, so a lower-only covariance (upper_stale) is not mirrored first; it writes both triangles.
+static int launch_usckf_wide(slk_filter *f, const KArgs &a0)
+{
+    KArgs a = a0;
+    const WideWs w = wide_ws(a.lay.N, a.m);
+    int rc = stage_reserve(f, f->ws_L, (size_t)a.B * w.total);
+    if (rc) return rc;
+    if (a.do_predict) {
+        KArgs p = a;                                   // the predict-only call: no measurement fields
+        p.do_update = 0; p.mm = 0; p.mp = nullptr; p.mp_stride = 0; p.z = nullptr; p.m = 0;
+        p.R = nullptr; p.r_stride = 0; p.gate = 0; p.Zext = nullptr;
+        rc = launch_usckf(f, p);
+        if (rc) return rc;
+        a.do_predict = 0;
+    }
+    a.wsL = f->ws_L.p;
+    hipLaunchKernelGGL(usckf_update_wide_kernel, dim3(a.B), dim3(256), 0, f->stream, a);
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+}
+
 static int launch_usckf(slk_filter *f, const KArgs &a)
 {
     int NT = (a.lay.N + 15) / 16;
@@ -517,6 +543,7 @@ static int launch_usckf(slk_filter *f, const KArgs &a)
     (void)NT; (void)f; (void)a;
     g_err = "development build: Msckf only"; return SLK_E_UNSUPPORTED;
 #else
+    if (a.m > MAXM && (a.do_update || a.emit == 4)) return launch_usckf_wide(f, a);      // any N, ahead of the split route
     const bool split = a.emit == 0 && a.lay.N <= 48;       // (usckf_predict_kernel stages 12 x N old rows and Fk in its 736 doubles of scratch)
     switch (NT) {
     case 3: return split ? launch_usckf_split(f, a) : launch_usckf_inst<3>(f, a);
@@ -571,7 +598,8 @@ static int fill_predict(slk_filter *f, KArgs &a, int model, const double *u, int
 static int fill_update(slk_filter *f, KArgs &a, int model, const double *params, int p_stride,
                        const double *z, int m, const double *R, int r_stride, int gate, int where)
 {
-    if (m < 1 || m > MAXM || !z || !R) return SLK_E_INVALID;
+    if (m < 1 || !z || !R) return SLK_E_INVALID;
+    if (f->lay.kind == SLK_MSCKF && m > MAXM) return SLK_E_INVALID;      // (Usckf: no row limit, slk_usckf_wide.hpp)
     if (r_stride != 0 && r_stride < m * m) return SLK_E_INVALID;
     if (f->lay.kind == SLK_MSCKF) {
         if (model != SLK_MM_FEATURE_PROJ && model != SLK_MM_POSE_POSITION && model != SLK_MODEL_EXTERNAL) return SLK_E_INVALID;

@@ -517,3 +517,4 @@ __global__ void usckf_set_measurement_kernel(const double *mean, const double *P
 
 #include "slk_usckf_fast.hpp"
 #include "slk_usckf_general.hpp"
+#include "slk_usckf_wide.hpp"

@@ -1,7 +1,9 @@
 """Throughput of the batched Usckf path (BASELINE config 1 shape: N = 48, m = 3, SPD variant).
 
-usage: python tools/bench_usckf.py [--nfk A] [--nfkl B] [batch ...]   (default 3 + 9 features: N = 48, m = 3; the
-state is N = 36 + A + B and the update has m = A rows, MM_VO_RELATIVE -- N > 96 runs on the global-workspace path)"""
+usage: python tools/bench_usckf.py [--nfk A] [--nfkl B] [--model vo|feature_proj] [--features F] [--no-cpu] [batch ...]
+(default 3 + 9 features: N = 48, m = 3; the state is N = 36 + A + B and the update has m = A rows, MM_VO_RELATIVE, or
+m = 2F rows, MM_FEATURE_PROJ with F features seen from poses 0, 1, 2 in turn -- N > 96 runs on the global-workspace path,
+m > 32 on the wide update)"""
 import argparse
 import os
 import sys
@@ -22,28 +24,39 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nfk", type=int, default=3)
     ap.add_argument("--nfkl", type=int, default=9)
+    ap.add_argument("--model", choices=("vo", "feature_proj"), default="vo")
+    ap.add_argument("--features", type=int, default=17)
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle rate")
     ap.add_argument("batches", type=int, nargs="*")
     args = ap.parse_args()
     nfk, nfkl, N = args.nfk, args.nfkl, 36 + args.nfk + args.nfkl
+    fp = args.model == "feature_proj"
+    m = 2 * args.features if fp else nfk
     batches = args.batches or [1024, 4096, 16384]
     for B in batches:
         s = sc.synthetic_usckf(B, nfk=nfk, nfkl=nfkl)
         f = slk.Usckf(mean=s["mean"], P=s["P"], nfk=nfk, nfkl=nfkl)
         dev = torch.device("cuda")
         u = torch.from_numpy(s["u"]).to(dev)
-        z = torch.from_numpy(s["z"]).to(dev)
+        mm, params, zz, RR = slk.MM_VO_RELATIVE, None, s["z"], s["R"]
+        if fp:
+            feat, zz = sc.usckf_features(s["mean"], poses=tuple(i % 3 for i in range(args.features)))
+            mm, params, RR = slk.MM_FEATURE_PROJ, torch.from_numpy(feat.reshape(B, -1)).to(dev), 0.01 * np.eye(m)
+        z = torch.from_numpy(np.ascontiguousarray(zz)).to(dev)
         Q = torch.from_numpy(np.ascontiguousarray(s["Q"].T)).to(dev)
-        R = torch.from_numpy(np.ascontiguousarray(s["R"].T)).to(dev)
+        R = torch.from_numpy(np.ascontiguousarray(RR.T)).to(dev)
         for _ in range(5):
-            f.step(slk.PM_CONST_VELOCITY, u, Q, z, slk.MM_VO_RELATIVE, None, R)
+            f.step(slk.PM_CONST_VELOCITY, u, Q, z, mm, params, R)
         f.sync()
         K = 100
         f.timer_start()
         for _ in range(K):
-            f.step(slk.PM_CONST_VELOCITY, u, Q, z, slk.MM_VO_RELATIVE, None, R)
+            f.step(slk.PM_CONST_VELOCITY, u, Q, z, mm, params, R)
         ms = f.timer_stop() / K
         bad = int(np.count_nonzero(f.status()))
-        print(f"Usckf N={N} m={nfk} B={B}: {B / ms * 1e3:.3e} filter-steps/s, {ms:.4f} ms/step, filters with status {bad}")
+        print(f"Usckf N={N} m={m} B={B}: {B / ms * 1e3:.3e} filter-steps/s, {ms:.4f} ms/step, filters with status {bad}")
+    if args.no_cpu or fp:
+        return
     s = sc.synthetic_usckf(64, nfk=nfk, nfkl=nfkl)
     t0 = time.perf_counter()
     n = 0
