@@ -274,6 +274,47 @@ namespace localization
         const _AugmentedState &muState() const { pull(); return mu_state; }                 // :518-521
         const AugmentedStateCovariance &PkAugmentedState() const { pull(); return Pk; }     // :523-526
 
+        /**@brief Normalised estimation error squared against `truth` on the tangent indices [t0, t0 + n) (n < 0: to
+         * getDOF()): e = truth [-] mu_state there, returns e^T Pss^-1 e with Pss that block of Pk (NaN if it is not
+         * positive definite); err, when given, receives e.  On the device (slk_nees); the filter is not modified. */
+        double nees(const _AugmentedState &truth, int t0 = 0, int n = -1, VectorizedAugmentedState *err = 0)
+        {
+            if ((int)truth.featuresk.size() != nfk || (int)truth.featuresk_l.size() != nfkl)
+                throw std::invalid_argument("Usckf::nees: the truth state has different feature blocks than the filter");
+            if (n < 0) n = h.N() - t0;
+            std::vector<double> t(h.Nq());
+            slk_store(truth, t.data());
+            double r = 0;
+            std::vector<double> e(err && n > 0 ? n : 0);
+            nees(t.data(), t0, n, &r, err ? e.data() : 0);
+            if (err) { err->resize(n); std::copy(e.begin(), e.end(), err->data()); }
+            return r;
+        }
+        /** raw form of slk_nees: truth [Nq] in the storage layout, nees [1], err [n] or null; `where` as in include/slk.h */
+        void nees(const double *truth, int t0, int n, double *nees_out, double *err = 0, int where = SLK_HOST)
+        {
+            slk::check(slk_nees(h.get(), truth, t0, n, nees_out, err, where), "slk_nees");
+        }
+        /**@brief S draws mu_state [+] L n_s from the filter's own Gaussian (L = chol(Pk), lower, the factor the sigma points
+         * come from): noise is N x S, one standard-normal column per draw.  All NaN if Pk is not positive definite. */
+        std::vector<_AugmentedState> sampleStates(const slk::Matrix &noise)
+        {
+            if (noise.rows() != h.N())
+                throw std::invalid_argument("Usckf::sampleStates: noise needs getDOF() rows, one column per draw");
+            const int S = noise.cols(), Nq = h.Nq();
+            std::vector<double> out((std::size_t)(S > 0 ? S : 0) * Nq);
+            sampleStates(noise.data(), S, out.data());
+            pull();
+            std::vector<_AugmentedState> xs((std::size_t)S, mu_state);
+            for (int s = 0; s < S; ++s) slk_load(xs[s], &out[(std::size_t)s * Nq], nfk, nfkl);
+            return xs;
+        }
+        /** raw form of slk_sample_states: noise [S][N], out [S][Nq] */
+        void sampleStates(const double *noise, int S, double *out, int where = SLK_HOST)
+        {
+            slk::check(slk_sample_states(h.get(), noise, S, out, where), "slk_sample_states");
+        }
+
         int status() { int s = 0; slk::check(slk_get_status(h.get(), &s, SLK_HOST), "slk_get_status"); return s; }
 
         template <typename _ScalarType>

@@ -254,6 +254,30 @@ int slk_msckf_drop_clone(slk_filter *f, int index);
  *      slk_update_sigma_points). ---- */
 int slk_check_sigma_points(slk_filter *f, double *max_cov_err, double *mean_err, int where);
 
+/* ---- Monte-Carlo consistency tools on the resident (mu, P) of every filter (the reference has no such call).
+ *      Both are read-only (mean, P, status bits and outlier counts stay as they were), read the LOWER triangle of P only
+ *      (a covariance whose strict upper triangle is stale after the exact-shape Msckf steps gives the same answer), run
+ *      at every N of both kinds, and enqueue one launch on the handle's stream (host outputs are synchronised).  A
+ *      (sub-)block that is not positive definite (a non-positive or NaN Cholesky pivot) gives that filter NaN outputs;
+ *      the others are unaffected, the call still returns SLK_OK and sets no status bit.
+ *      Both reserve, per filter, (n+1)(n+2)/2 + 33 * (n + 1 rounded up to 16) doubles (rounded up to 8; n = N for
+ *      slk_sample_states), kept by the handle between calls; a failed reservation returns before any launch.
+ *
+ *      slk_nees: normalised estimation error squared on the tangent indices [t0, t0 + n):
+ *        e = (truth [-] mu) restricted to the range (truth [B][Nq] in the storage layout; [-] is exactly the filter's
+ *        own boxminus, log(mu^-1 q) for every SO(3) block, w < 0 included; a range may start or end inside an SO(3)
+ *        block: its components come from that block's full 3-vector),
+ *        nees [B] = e^T P_ss^-1 e with P_ss the principal n x n block of P on the range,
+ *        err [B][n] = e when not NULL.
+ *        SLK_E_INVALID for t0 < 0, n < 1, t0 + n > N or a NULL truth / nees.
+ *      slk_sample_states: out [B][S][Nq] = mu_b [+] (L_b noise[b][s]) for noise [B][S][N] supplied by the caller (the
+ *        library has no RNG: e.g. standard normal draws made on the device), L_b the lower Cholesky factor of P_b -- the
+ *        factor the sigma points are drawn from.  A non-positive-definite P_b fills all S rows of that filter with NaN.
+ *        SLK_E_INVALID for S < 1 or a NULL noise / out. ---- */
+int slk_nees(slk_filter *f, const double *truth /*[B][Nq]*/, int t0, int n, double *nees /*[B]*/,
+             double *err /*[B][n] or NULL*/, int where);
+int slk_sample_states(slk_filter *f, const double *noise /*[B][S][N]*/, int S, double *out /*[B][S][Nq]*/, int where);
+
 /* ---- arithmetic of the covariance rebuild (Msckf.hpp:665 -> :574-589): SLK_PREC_F64 (default, the
  *      parity path), SLK_PREC_F32 (fp32 MFMA) or SLK_PREC_BF16 (bf16 operands, fp32 accumulation).
  *      The reduced modes exist for the tolerance sweep of BASELINE.json config 5; the reference is

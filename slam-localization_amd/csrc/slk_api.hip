@@ -19,6 +19,7 @@
 #include "slk_ekf.hpp"
 #include "slk_ekf_tiles.hpp"
 #include "slk_pose.hpp"
+#include "slk_consistency.hpp"
 
 // The largest step-kernel instantiations are compiled in translation units of their own (slk_inst_big.hip,
 // slk_inst_mid.hip) so that the library's build runs them in parallel; development builds (one file) keep none of them.
@@ -66,6 +67,7 @@ struct slk_filter {
     Stage st_u, st_Q, st_mp, st_z, st_R, st_X, st_Z, st_tmpP, st_tmpM;
     Stage ws_L, ws_DR;            // large-state workspaces (N > 80), allocated on first use
     Stage ws_ekf;                 // EKF update workspace, allocated on first use
+    Stage ws_cons;                // slk_nees / slk_sample_states workspace (consistency_ws), allocated on first use
     // Msckf rotation-item descriptors, one table per window length k the handle has run (a sliding window alternates
     // between k and k + 1: the tables stay, so the steady state allocates and synchronises nothing)
     struct Rtab { unsigned long long *dev = nullptr; std::vector<unsigned long long> host; };
@@ -167,7 +169,7 @@ void slk_destroy(slk_filter *f)
     (void)hipSetDevice(f->cfg.device);
     (void)hipStreamSynchronize(f->stream);
     Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_X, &f->st_Z, &f->st_tmpP, &f->st_tmpM,
-                   &f->ws_L, &f->ws_DR, &f->ws_ekf};
+                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_cons};
     for (Stage *s : st) if (s->p) (void)hipFree(s->p);
     for (auto &kv : f->rtabs) if (kv.second.dev) (void)hipFree(kv.second.dev);
     if (f->d_mean) (void)hipFree(f->d_mean);
@@ -1231,6 +1233,70 @@ int slk_check_sigma_points(slk_filter *f, double *max_cov_err, double *mean_err,
     HIPCHECK(hipMemcpyAsync(max_cov_err, res, B * sizeof(double), kind, f->stream));
     HIPCHECK(hipMemcpyAsync(mean_err, res + B, B * sizeof(double), kind, f->stream));
     if (where == SLK_HOST) HIPCHECK(hipStreamSynchronize(f->stream));
+    return SLK_OK;
+}
+
+// Consistency tools (slk_consistency.hpp).  Every argument is checked and every buffer reserved before the one launch;
+// the kernels read the lower triangle of P only, so a lower-only covariance (upper_stale) is not mirrored first.
+int slk_nees(slk_filter *f, const double *truth, int t0, int n, double *nees, double *err, int where)
+{
+    if (!f || !truth || !nees || t0 < 0 || n < 1 || n > f->lay.N - t0) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t B = (size_t)f->B;
+    int rc = stage_reserve(f, f->ws_cons, B * consistency_ws(n).total);
+    if (rc) return rc;
+    double *dn = nees, *de = err;
+    if (where == SLK_HOST) {
+        rc = stage_reserve(f, f->st_tmpM, B + (err ? B * n : 0));
+        if (rc) return rc;
+        dn = f->st_tmpM.p;
+        de = err ? f->st_tmpM.p + B : nullptr;
+    }
+    const double *dt = nullptr;
+    rc = stage_in(f, f->st_u, truth, B * f->lay.Nq, where, &dt);
+    if (rc) return rc;
+#ifdef SLK_DEV_N60
+    g_err = "development build: no consistency kernels"; return SLK_E_UNSUPPORTED;
+#else
+    hipLaunchKernelGGL(nees_kernel, dim3(f->B), dim3(256), 0, f->stream, f->lay, (const double *)f->d_mean,
+                       (const double *)f->d_P, dt, t0, n, dn, de, f->ws_cons.p);
+    HIPCHECK(hipGetLastError());
+#endif
+    if (where == SLK_HOST) {
+        HIPCHECK(hipMemcpyAsync(nees, dn, B * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (err) HIPCHECK(hipMemcpyAsync(err, de, B * n * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        HIPCHECK(hipStreamSynchronize(f->stream));
+    }
+    return SLK_OK;
+}
+
+int slk_sample_states(slk_filter *f, const double *noise, int S, double *out, int where)
+{
+    if (!f || !noise || !out || S < 1) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t B = (size_t)f->B, N = (size_t)f->lay.N, Nq = (size_t)f->lay.Nq;
+    int rc = stage_reserve(f, f->ws_cons, B * consistency_ws(f->lay.N).total);
+    if (rc) return rc;
+    double *dout = out;
+    if (where == SLK_HOST) {
+        rc = stage_reserve(f, f->st_X, B * S * Nq);
+        if (rc) return rc;
+        dout = f->st_X.p;
+    }
+    const double *dn = nullptr;
+    rc = stage_in(f, f->st_Z, noise, B * S * N, where, &dn);
+    if (rc) return rc;
+#ifdef SLK_DEV_N60
+    g_err = "development build: no consistency kernels"; return SLK_E_UNSUPPORTED;
+#else
+    hipLaunchKernelGGL(sample_states_kernel, dim3(f->B), dim3(256), 0, f->stream, f->lay, (const double *)f->d_mean,
+                       (const double *)f->d_P, dn, S, dout, f->ws_cons.p);
+    HIPCHECK(hipGetLastError());
+#endif
+    if (where == SLK_HOST) {
+        HIPCHECK(hipMemcpyAsync(out, dout, B * S * Nq * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        HIPCHECK(hipStreamSynchronize(f->stream));
+    }
     return SLK_OK;
 }
 

@@ -32,7 +32,8 @@ EXPORTS = [
     "slk_get_outliers", "slk_get_status", "slk_clear_status", "slk_sync", "slk_timer_start", "slk_timer_stop",
     "slk_selftest_mfma", "slk_set_rebuild_precision", "slk_dead_reckon", "slk_msckf_clone_pose", "slk_msckf_drop_clone", "slk_update_ekf",
     "slk_check_sigma_points", "slk_update_innovation", "slk_update_selected", "slk_transform_compose",
-    "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix",
+    "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix", "slk_nees",
+    "slk_sample_states",
 ]
 
 
@@ -98,6 +99,8 @@ def load_library(path=None):
     lib.slk_adaptive_destroy.argtypes = [vp]
     lib.slk_adaptive_destroy.restype = None
     lib.slk_adaptive_matrix.argtypes = [vp, ip, vp, vp, vp, vp, vp, ip, vp, ip]
+    lib.slk_nees.argtypes = [vp, vp, ip, ip, vp, vp, ip]
+    lib.slk_sample_states.argtypes = [vp, vp, ip, vp, ip]
     if path is None:
         _lib = lib
     return lib
@@ -358,6 +361,71 @@ class _FilterBatch:
         _check(self._lib.slk_dead_reckon_pose(self._h, ua.ptr, ua.stride, vca.ctypes.data, cs, pv.ctypes.data, po.ctypes.data,
                                               de.ctypes.data, int(bool(use_tf)), HOST), "slk_dead_reckon_pose")
         return po, de
+
+    def nees(self, truth, t0=0, n=None, error=False):
+        """Normalised estimation error squared of every filter on the tangent indices [t0, t0 + n) (default: to N):
+        e = (truth [-] mu) on the range, nees [B] = e^T P_ss^-1 e with P_ss the principal block of P there.  truth
+        [B, Nq] (or one shared row) in the storage layout.  error=True returns (nees, e [B, n]).  A block that is not
+        positive definite gives NaN for that filter.  numpy in -> numpy out; a torch device tensor in -> torch device
+        tensors out (truth [B, Nq], contiguous float64; torch's stream is synchronised before the call, the handle's
+        after it)."""
+        n = self.N - int(t0) if n is None else int(n)
+        B = self.B
+        if truth is None:
+            tp, where, dev = None, HOST, None
+        elif _is_dev(truth):
+            if not truth.is_contiguous() or truth.numel() != B * self.Nq or str(truth.dtype) != "torch.float64":
+                raise SlkError(f"nees: truth must be a contiguous [{B}, {self.Nq}] tensor, got {tuple(truth.shape)}")
+            tp, where, dev = truth.data_ptr(), DEVICE, truth.device
+        else:
+            truth = np.asarray(truth, dtype=np.float64)
+            if truth.shape[-1] != self.Nq or truth.ndim > 2 or (truth.ndim == 2 and truth.shape[0] not in (1, B)):
+                raise SlkError(f"nees: truth must be [{B}, {self.Nq}], got {truth.shape}")
+            truth = np.ascontiguousarray(np.broadcast_to(truth.reshape(-1, self.Nq), (B, self.Nq)))
+            tp, where, dev = truth.ctypes.data, HOST, None
+        ne = max(n, 0)
+        if where == DEVICE:
+            import torch
+            torch.cuda.current_stream(dev).synchronize()      # (the handle's stream does not wait for torch's)
+            out = torch.empty(B, dtype=torch.float64, device=dev)
+            err = torch.empty((B, ne), dtype=torch.float64, device=dev) if error else None
+            optr, eptr = out.data_ptr(), (err.data_ptr() if error else None)
+        else:
+            out = np.empty(B)
+            err = np.empty((B, ne)) if error else None
+            optr, eptr = out.ctypes.data, (err.ctypes.data if error else None)
+        _check(self._lib.slk_nees(self._h, tp, int(t0), n, optr, eptr, where), "slk_nees")
+        if where == DEVICE:
+            self.sync()                                        # torch may read the outputs on any stream
+        return (out, err) if error else out
+
+    def sample_states(self, noise):
+        """Gaussian draws from every filter's own (mu, P): out [B, S, Nq] = mu [+] (L n) for noise [B, S, N] (e.g. standard
+        normal), L the lower Cholesky factor of P (the factor the sigma points are drawn from).  A P that is not
+        positive definite fills that filter's rows with NaN.  numpy in -> numpy out; a torch device tensor in -> a
+        torch device tensor out."""
+        B, N, Nq = self.B, self.N, self.Nq
+        if noise is None:
+            _check(self._lib.slk_sample_states(self._h, None, 1, None, HOST), "slk_sample_states")
+        if not _is_dev(noise):
+            noise = np.asarray(noise, dtype=np.float64)
+        if noise.ndim != 3 or noise.shape[0] != B or noise.shape[2] != N:
+            raise SlkError(f"sample_states: noise must be [{B}, S, {N}], got {tuple(noise.shape)}")
+        S = int(noise.shape[1])
+        if _is_dev(noise):
+            import torch
+            if not noise.is_contiguous() or str(noise.dtype) != "torch.float64":
+                raise SlkError("sample_states: noise must be a contiguous float64 tensor")
+            torch.cuda.current_stream(noise.device).synchronize()
+            out = torch.empty((B, max(S, 0), Nq), dtype=torch.float64, device=noise.device)
+            _check(self._lib.slk_sample_states(self._h, noise.data_ptr(), S, out.data_ptr(), DEVICE), "slk_sample_states")
+            self.sync()
+            return out
+        nz = np.ascontiguousarray(noise, dtype=np.float64)
+        out = np.empty((B, max(S, 0), Nq))
+        _check(self._lib.slk_sample_states(self._h, nz.ctypes.data if S > 0 else None, S, out.ctypes.data, HOST),
+               "slk_sample_states")
+        return out
 
     def predict_functor(self, f, Q):
         """predict(f, Q) with an arbitrary Python callable f: state[13] -> state[13], applied on the host."""
