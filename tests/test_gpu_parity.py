@@ -670,6 +670,17 @@ def test_strict_upper_triangle_is_completed_on_demand(slk, k):
     Ph = h.getPk()
     assert np.abs(Ph - np.transpose(Ph, (0, 2, 1))).max() == 0.0
     np.testing.assert_array_equal(Ph[:, :N, :N], P)
+    # the EKF update right after the steps (its kernels read the whole matrix) == the same update on a handle that was
+    # given the whole matrix through the host
+    e = sc.synthetic_ekf(B, k, N + 8, seed=4321 + k, outliers=False)
+    a = stepped(3)
+    a.update_ekf(e["z"], e["zmean"], e["H"], e["R"], gate=False)
+    c = slk.Msckf(f.muState(), P)
+    c.update_ekf(e["z"], e["zmean"], e["H"], e["R"], gate=False)
+    assert (a.status() == 0).all() and (c.status() == 0).all()
+    np.testing.assert_array_equal(a.outliers(), c.outliers())
+    np.testing.assert_array_equal(a.muState(), c.muState())
+    np.testing.assert_array_equal(a.getPk(), c.getPk())
 
 
 def test_msckf_device_side_window_sliding(slk):
