@@ -176,10 +176,10 @@ int  slk_adaptive_matrix(slk_adaptive *a, int n, const double *xk, const double 
  *      params [B][p_stride] model parameters (0 = shared), z [B][m], R m x m (r_stride 0 = shared).
  *      gate: Msckf 0 = accept all blocks, 1 = accept_mahalanobis_distance (Msckf.hpp:199,844-905);
  *            Usckf 0 = accept_any (Usckf.hpp:249), d = chi-square dof of the whole-vector gate.
- *      Usckf limits: N = 36 + nfk + nfkl > 96 runs on the global-workspace path (one workgroup per filter, predict and
- *      update as two launches) with no state-size limit except device memory: it reserves, per filter,
- *      N^2 + N(N+1)/2 + (2N+1)(m + 9) + 3Nm + 3m^2 + 3m + 2Nq + 5N + 512 doubles (rounded up to 8; m = 1 for
- *      slk_update_sigma_points), kept by the handle between calls.  N <= 96: for N > 48 the state and the update's
+ *      Usckf limits: N = 36 + nfk + nfkl > 96 has no state-size limit except device memory: the predict runs on a
+ *      global-workspace kernel (one wave per filter), and every update-side call (slk_update, slk_step,
+ *      slk_update_from_sigma, slk_update_innovation, slk_update_sigma_points) on the wide update described below, with
+ *      its reservation (m = 1 for slk_update_sigma_points).  N <= 96: for N > 48 the state and the update's
  *      measurement arrays share one workgroup's LDS; a call whose carve exceeds 160 KiB is refused with
  *      SLK_E_UNSUPPORTED before any launch, the filter untouched (slk_step too).  At m = nfk (SLK_MM_VO_RELATIVE) that
  *      refuses e.g. N = 96 with nfk = 12, N = 90 with nfk = 18 and N = 80 with nfk = 24; m = 3 / 4 (pose position, two

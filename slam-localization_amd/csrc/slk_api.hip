@@ -489,34 +489,13 @@ static int launch_usckf_split(slk_filter *f, const KArgs &a0)
 }
 #endif
 
-// N > 96: any state size, everything N-sized in a global workspace (slk_usckf_general.hpp).  Predict (or its Tier-B
-// emission) and update are launches of their own: a step is two.
-static int launch_usckf_general(slk_filter *f, const KArgs &a0)
-{
-    KArgs a = a0;
-    const bool upd = a.do_update || a.emit == 2 || a.emit == 4;
-    if (a.do_predict || a.emit == 1) {
-        hipLaunchKernelGGL(usckf_predict_general_kernel, dim3(a.B), dim3(64), 0, f->stream, a);
-        HIPCHECK(hipGetLastError());
-        if (a.emit == 1 || !upd) return SLK_OK;
-        a.do_predict = 0;
-    }
-    if (!upd) return SLK_OK;
-    const GenWs w = general_ws(a.lay.N, a.lay.Nq, 3, a.m > 0 ? a.m : 1, true);
-    int rc = stage_reserve(f, f->ws_L, (size_t)a.B * w.total);
-    if (rc) return rc;
-    a.wsL = f->ws_L.p;
-    hipLaunchKernelGGL(usckf_update_general_kernel, dim3(a.B), dim3(256), 0, f->stream, a);
-    HIPCHECK(hipGetLastError());
-    return SLK_OK;
-}
-
 static int launch_usckf(slk_filter *f, const KArgs &a);
 
-// m > MAXM measurement rows, any N (slk_usckf_wide.hpp).  The workspace is reserved before anything is launched (a failed
-// reservation leaves the filter untouched).  The predict half of a step takes the route a predict-only call takes at this
-// N, then the update is a launch of its own: a step is bit-identical to predict followed by update.  The wide kernel reads
-// the lower triangle of P only, so a lower-only covariance (upper_stale) is not mirrored first; it writes both triangles.
+// Every update-side call the LDS-resident kernels do not take: m > MAXM rows at any N, and any m at N > 96
+// (slk_usckf_wide.hpp).  The workspace is reserved before anything is launched (a failed reservation leaves the filter
+// untouched).  The predict half of a step takes the route a predict-only call takes at this N, then the update is a
+// launch of its own: a step is bit-identical to predict followed by update.  The wide kernel reads the lower triangle of
+// P only, so a lower-only covariance (upper_stale) is not mirrored first; it writes both triangles.
 static int launch_usckf_wide(slk_filter *f, const KArgs &a0)
 {
     KArgs a = a0;
@@ -545,14 +524,18 @@ static int launch_usckf(slk_filter *f, const KArgs &a)
     (void)NT; (void)f; (void)a;
     g_err = "development build: Msckf only"; return SLK_E_UNSUPPORTED;
 #else
-    if (a.m > MAXM && (a.do_update || a.emit == 4)) return launch_usckf_wide(f, a);      // any N, ahead of the split route
+    const bool upd = a.do_update || a.emit == 2 || a.emit == 4;
+    if (upd && (a.m > MAXM || a.lay.N > 96)) return launch_usckf_wide(f, a);      // ahead of the split route
     const bool split = a.emit == 0 && a.lay.N <= 48;       // (usckf_predict_kernel stages 12 x N old rows and Fk in its 736 doubles of scratch)
     switch (NT) {
     case 3: return split ? launch_usckf_split(f, a) : launch_usckf_inst<3>(f, a);
     case 4: return launch_usckf_inst<4>(f, a);
     case 5: return launch_usckf_inst<5>(f, a);
     case 6: return launch_usckf_inst<6>(f, a);
-    default: return launch_usckf_general(f, a);      // N > 96: any state size, everything in a global workspace
+    default:                                    // N > 96, predict or its sigma points (emit 1): P stays in global memory
+        hipLaunchKernelGGL(usckf_predict_general_kernel, dim3(a.B), dim3(64), 0, f->stream, a);
+        HIPCHECK(hipGetLastError());
+        return SLK_OK;
     }
 #endif
 }

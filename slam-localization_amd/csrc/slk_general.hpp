@@ -14,10 +14,8 @@
 
 namespace slk {
 
-// packed: a copy of the factor in the packed layout of the LDS kernels as well (the Usckf path, slk_usckf_general.hpp, hands it
-// to their measurement models)
-struct GenWs { size_t L, Z, DZ, Cxz, K, Sm, G, zbar, innov, mu, ref, delta, md, wgt, DR, red, Lp, total; };
-__host__ __device__ inline GenWs general_ws(int N, int Nq, int nso3, int m, bool packed = false)
+struct GenWs { size_t L, Z, DZ, Cxz, K, Sm, G, zbar, innov, mu, ref, delta, md, wgt, DR, red, total; };
+__host__ __device__ inline GenWs general_ws(int N, int Nq, int nso3, int m)
 {
     GenWs w;
     const size_t S = 2 * (size_t)N + 1;
@@ -38,7 +36,6 @@ __host__ __device__ inline GenWs general_ws(int N, int Nq, int nso3, int m, bool
     w.wgt = o;   o += (size_t)nso3 * N;            // atan-wrap factor per (block, column)
     w.DR = o;    o += 3 * (size_t)nso3 * S;        // rotation deviations of every sigma point
     w.red = o;   o += 512;
-    w.Lp = o;    o += packed ? (size_t)N * (N + 1) / 2 : 0;
     w.total = (o + 7) & ~(size_t)7;
     return w;
 }

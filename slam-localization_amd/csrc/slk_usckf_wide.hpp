@@ -1,10 +1,12 @@
-// slk_usckf_wide.hpp -- Usckf::update (reference src/filters/Usckf.hpp:246-308) with more than MAXM = 32 measurement rows,
-// at any state size.  The reference's measurement dimension is ukfom::dof<_Measurement> and its feature blocks are dynamic
-// (State.hpp:529-593): nothing bounds m but memory.  One 256-thread workgroup (4 waves) per filter; every N- and m-sized
-// array lives in a per-filter global workspace (wide_ws), LDS holds only the 16 x 16 diagonal tiles of the two factors.
-// The order of operations is that of usckf_update_general_kernel; the products that grow with m run on fp64 MFMA
+// slk_usckf_wide.hpp -- Usckf::update (reference src/filters/Usckf.hpp:246-308) for every call the LDS-resident
+// usckf_kernel does not take: more than MAXM = 32 measurement rows at any state size, and any update-side call (update,
+// emit 2, emit 4) at N = 36 + nfk + nfkl > 96.  The reference's measurement dimension is ukfom::dof<_Measurement> and its
+// feature blocks are dynamic (State.hpp:529-593): nothing bounds m or N but memory.  One 256-thread workgroup (4 waves) per
+// filter; every N- and m-sized array lives in a per-filter global workspace (wide_ws), LDS holds only the 16 x 16 diagonal
+// tiles of the two factors.  Every tile is masked by the true N and m, so any m >= 1 works.  The products run on fp64 MFMA
 // (16 x 16 x 4, C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg, as chol_blocked_mem):
 //   L = chol(P), packed lower      chol_blocked_mem, reads the LOWER triangle of P only
+//   emit 2                         the update sigma points X from L (pert / sigma_quat), nothing else
 //   Z = h(X), 2N + 1 sigma points  measure_item / pert / sigma_quat; EXTERNAL reads Zext in place
 //   S = 1/2 sum dZ_i dZ_i^T + R    SYRK on the 16 x 16 lower tiles, k = sigma index (padded to 4)
 //   covXZ = 1/2 (W o L) dZ^T       dZ_j = Z_{2j+1} - Z_{2j+2}; k runs over the nonzero columns of the row tile only
@@ -13,8 +15,8 @@
 //                                  MFMA, the diagonal block one thread per row
 //   gate, delta = K nu, P -= covXZ K^T (lower tiles, both triangles written from one value), direct boxplus
 // Status bits, outlier counts, the emit-4 output ([S column-major, innovation]) and the whole-vector gate as in
-// usckf_update_general_kernel.  P is read from its lower triangle only, so the lower-only covariance the N = 48 split
-// predict leaves (slk_filter::upper_stale) needs no mirror first.
+// usckf_kernel<NT, 256>.  P is read from its lower triangle only, so the lower-only covariance the N = 48 split predict
+// leaves (slk_filter::upper_stale) needs no mirror first.
 #pragma once
 // (included at the end of slk_usckf.hpp, after slk_usckf_general.hpp)
 
@@ -43,7 +45,7 @@ __host__ __device__ inline WideWs wide_ws(int N, int m)
     return w;
 }
 
-// usckf_wrap_weight on the packed factor
+// X_i [-] mu of rotation block b along column j of the packed factor: MTK's log uses atan, a column longer than pi wraps
 __device__ __forceinline__ double usckf_wrap_weight_pk(const double *Lp, int N, int t0, int j)
 {
     const double v0 = Lz(Lp, N, t0, j), v1 = Lz(Lp, N, t0 + 1, j), v2 = Lz(Lp, N, t0 + 2, j);
@@ -79,7 +81,7 @@ __device__ __forceinline__ void wide_diag_tile(const double *Gp, int m, int C, d
     }
 }
 
-// Usckf::update (:246-308) for m > MAXM rows, any N.  One 256-thread workgroup per filter.
+// Usckf::update (:246-308) and its sigma points (emit 2), any N and m.  One 256-thread workgroup per filter.
 __global__ __launch_bounds__(256) void usckf_update_wide_kernel(KArgs a)
 {
     __shared__ __attribute__((aligned(16))) double cb[4 * 34 + 152];     // chol_blocked_mem: diagonal tile factor, pivots
@@ -107,6 +109,18 @@ __global__ __launch_bounds__(256) void usckf_update_wide_kernel(KArgs a)
     SLK_STAMP_NR(1);
     if (fail >= 0) {
         status |= SLK_ST_LLT_FAIL;                          // the filter is left unchanged
+    } else if (a.emit == 2) {
+        double *X = a.Xout + (size_t)bidx * S * Nq;
+        for (size_t e = tid; e < (size_t)S * N; e += 256) {
+            const int t = (int)(e % N), i = (int)(e / N);
+            int blk = 0, comp = 0;
+            const int s = t2s(L, t, blk, comp);
+            if (s >= 0) X[(size_t)i * Nq + s] = mu[s] + pert(Lp, N, nullptr, t, sig_of(i));
+        }
+        for (size_t e = tid; e < (size_t)S * 3; e += 256) {
+            const int b = (int)(e % 3), i = (int)(e / 3);
+            stq(X + (size_t)i * Nq + so3_soff(L, b), sigma_quat(L, mu, Lp, nullptr, b, sig_of(i)));
+        }
     } else if (!pose_params_ok(a, L, a.mp ? a.mp + (size_t)bidx * a.mp_stride : nullptr)) {
         status |= SLK_ST_BAD_INDEX;                         // pose index out of 0..2: update skipped
     } else {

@@ -1,7 +1,7 @@
-"""Usckf with more than 96 state dimensions (N = 36 + nfk + nfkl > 96): the global-workspace predict and update kernels
-(csrc/slk_usckf_general.hpp, launch_usckf_general in csrc/slk_api.hip) and setMeasurement past 96, against the fp64 CPU
-oracle with the helpers and the tolerance of test_gpu_routes.py.  Every case here was refused with SlkError before that
-path existed.  Run with `pytest -m gpu` on an MI355X.
+"""Usckf with more than 96 state dimensions (N = 36 + nfk + nfkl > 96): the global-workspace predict kernel
+(csrc/slk_usckf_general.hpp), every update-side call on the wide update kernel (csrc/slk_usckf_wide.hpp, launch_usckf_wide
+in csrc/slk_api.hip) and setMeasurement past 96, against the fp64 CPU oracle with the helpers and the tolerance of
+test_gpu_routes.py.  Every case here was refused with SlkError before N > 96 was supported.  Run with `pytest -m gpu` on an MI355X.
 """
 import numpy as np
 import pytest

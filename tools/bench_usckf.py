@@ -2,8 +2,8 @@
 
 usage: python tools/bench_usckf.py [--nfk A] [--nfkl B] [--model vo|feature_proj] [--features F] [--no-cpu] [batch ...]
 (default 3 + 9 features: N = 48, m = 3; the state is N = 36 + A + B and the update has m = A rows, MM_VO_RELATIVE, or
-m = 2F rows, MM_FEATURE_PROJ with F features seen from poses 0, 1, 2 in turn -- N > 96 runs on the global-workspace path,
-m > 32 on the wide update)"""
+m = 2F rows, MM_FEATURE_PROJ with F features seen from poses 0, 1, 2 in turn -- N > 96 runs the predict on the
+global-workspace kernel, and N > 96 or m > 32 the update on the wide kernel)"""
 import argparse
 import os
 import sys
