@@ -222,6 +222,46 @@ int slk_step(slk_filter *f, int pmodel, const double *u, int u_stride, const dou
              int mmodel, const double *params, int p_stride, const double *z, int m,
              const double *R, int r_stride, int gate, int where);
 
+/* ---- multi-step trajectories: T fused steps in one call (the reference has no such call: its callers loop over
+ *      predict / update).  After the call the mean, P (as slk_get_state reads it), the status bits and the outlier
+ *      counts are bit-identical to T successive slk_step calls with the same inputs; a filter whose factorisation fails
+ *      at step t is left unchanged by that step and gets its status bit, the next steps go on.
+ *      Per-step inputs: step t reads X + t * X_tstride for X = u, Q, params, z, R (and truth); each block has exactly the
+ *      layout of the matching slk_step argument with the same *_stride meaning.  A *_tstride counts doubles; 0 = every
+ *      step uses the same block; a nonzero one shorter than one step's block is SLK_E_INVALID.
+ *      Optional records (NULL = not recorded), all [T][B]-major:
+ *        mean_hist     [T][B][Nq]  the mean after step t (what slk_get_state returns after the (t + 1)-th single step)
+ *        outliers_hist [T][B]      what slk_get_outliers returns after step t
+ *        nees_hist     [T][B]      slk_nees(truth_t, nees_t0, nees_n) after step t; truth_t = truth + t * truth_tstride,
+ *                                  [B][Nq] (needs truth; the range rules of slk_nees)
+ *      Every check runs before any launch (slk_step's checks for every step, T >= 1, where SLK_HOST or SLK_DEVICE, nees_hist needs truth; Msckf
+ *      m > 32 and SLK_MODEL_EXTERNAL are refused as in slk_step), and every staging / workspace reservation is made
+ *      before the first launch: a failed check or reservation leaves the filter untouched.
+ *      SLK_HOST: one upload of each input for all T steps, one synchronised download of the records at the end.
+ *      SLK_DEVICE: nothing is copied; asynchronous on the handle's stream.  No host synchronisation between steps.
+ *      Each step enqueues slk_step's own launches on the inputs of that step, then that step's records: device-to-device
+ *      copies of the mean / outlier counts, and the NEES from a one-wave register factorisation for ranges of n <= 30
+ *      (equal to slk_nees to 1e-10 relative, NaN exactly where slk_nees gives NaN) or from slk_nees's own kernel for
+ *      wider ranges (bit-identical; its workspace reserved once).
+ *      Memory: the host route stages all T steps of every input and of the records in device buffers of the handle,
+ *      which keeps them (like every staging buffer) until slk_destroy -- e.g. the mean records alone are T * B * Nq
+ *      doubles (450 MB at T = 200, B = 4096, N = 60).  The device route allocates nothing per step. ---- */
+typedef struct slk_traj {
+    int T;                                                            /* number of steps, >= 1 */
+    int pmodel; const double *u; int u_stride; long long u_tstride;   /* step t reads u + t * u_tstride */
+    const double *Q; int q_stride; long long q_tstride;
+    int mmodel; const double *params; int p_stride; long long p_tstride;
+    const double *z; int m; long long z_tstride;                      /* per step [B][m], as slk_step */
+    const double *R; int r_stride; long long r_tstride;
+    int gate;
+    /* optional per-step records (NULL = not recorded) */
+    double   *mean_hist;      /* [T][B][Nq]: the mean after step t */
+    unsigned *outliers_hist;  /* [T][B]: what slk_get_outliers returns after step t */
+    const double *truth; long long truth_tstride; int nees_t0, nees_n;  /* truth of step t: truth + t * truth_tstride, [B][Nq] */
+    double   *nees_hist;      /* [T][B]: slk_nees(truth_t, nees_t0, nees_n) after step t (needs truth) */
+} slk_traj;
+int slk_step_n(slk_filter *f, const slk_traj *t, int where);
+
 /* ---- Tier B (opaque host functors, the reference's boost::bind form:
  *      UsckfUnitTest.cpp:246,284; MsckfUnitTest.cpp:200-205).  The library draws the sigma
  *      points (generateSigmaPoints, Msckf.hpp:400-468 / Usckf.hpp:532-598), the caller applies

@@ -20,6 +20,7 @@
 #include "slk_ekf_tiles.hpp"
 #include "slk_pose.hpp"
 #include "slk_consistency.hpp"
+#include "slk_trajectory.hpp"
 
 // The largest step-kernel instantiations are compiled in translation units of their own (slk_inst_big.hip,
 // slk_inst_mid.hip) so that the library's build runs them in parallel; development builds (one file) keep none of them.
@@ -68,6 +69,7 @@ struct slk_filter {
     Stage ws_L, ws_DR;            // large-state workspaces (N > 80), allocated on first use
     Stage ws_ekf;                 // EKF update workspace, allocated on first use
     Stage ws_cons;                // slk_nees / slk_sample_states workspace (consistency_ws), allocated on first use
+    Stage st_truth, st_rec;       // slk_step_n (host route): the truths of all steps, the device copy of the records
     // Msckf rotation-item descriptors, one table per window length k the handle has run (a sliding window alternates
     // between k and k + 1: the tables stay, so the steady state allocates and synchronises nothing)
     struct Rtab { unsigned long long *dev = nullptr; std::vector<unsigned long long> host; };
@@ -169,7 +171,7 @@ void slk_destroy(slk_filter *f)
     (void)hipSetDevice(f->cfg.device);
     (void)hipStreamSynchronize(f->stream);
     Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_X, &f->st_Z, &f->st_tmpP, &f->st_tmpM,
-                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_cons};
+                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_cons, &f->st_truth, &f->st_rec};
     for (Stage *s : st) if (s->p) (void)hipFree(s->p);
     for (auto &kv : f->rtabs) if (kv.second.dev) (void)hipFree(kv.second.dev);
     if (f->d_mean) (void)hipFree(f->d_mean);
@@ -241,6 +243,19 @@ static int ensure_dynamic_lds(const void *kern, int device, size_t lds)
 }
 
 // ---------------------------------------------------------------------------- launch helpers
+// Msckf rotation-item descriptors of window length lay.k (W items, carve_step's W)
+static int ensure_rtab(slk_filter *f, const Lay &lay, int W)
+{
+    slk_filter::Rtab &rt = f->rtabs[lay.k];
+    if (!rt.dev) {                             // first step at this window length: build the table, copy it on the stream
+        rt.host.resize((size_t)W);             // (the host copy lives as long as the handle: the copy needs no wait)
+        for (int w = 0; w < W; ++w) rt.host[w] = rot_item_descriptor(lay.N, w);
+        HIPCHECK(hipMalloc(&rt.dev, rt.host.size() * sizeof(unsigned long long)));
+        HIPCHECK(hipMemcpyAsync(rt.dev, rt.host.data(), rt.host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, f->stream));
+    }
+    return SLK_OK;
+}
+
 template <int NT, int NTHREADS, int KST = -1, int MST = 0>
 static int launch_msckf_inst(slk_filter *f, const KArgs &a0)
 {
@@ -248,18 +263,14 @@ static int launch_msckf_inst(slk_filter *f, const KArgs &a0)
     constexpr bool BIG = NT > 4;
     Carve cv = carve_step(a.lay, a.m, NT, BIG, a.rebuild_prec);
     {
-        slk_filter::Rtab &rt = f->rtabs[a.lay.k];
-        if (!rt.dev) {                             // first step at this window length: build the table, copy it on the stream
-            rt.host.resize((size_t)cv.W);          // (the host copy lives as long as the handle: the copy needs no wait)
-            for (int w = 0; w < cv.W; ++w) rt.host[w] = rot_item_descriptor(a.lay.N, w);
-            HIPCHECK(hipMalloc(&rt.dev, rt.host.size() * sizeof(unsigned long long)));
-            HIPCHECK(hipMemcpyAsync(rt.dev, rt.host.data(), rt.host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, f->stream));
-        }
-        a.rtab = rt.dev;
+        int rc = ensure_rtab(f, a.lay, cv.W);
+        if (rc) return rc;
+        a.rtab = f->rtabs[a.lay.k].dev;
     }
     if constexpr (NT >= 3 && NT <= 4) {
         // Three launches per step: predict (one wave per filter), the first factorisation (its own residency, the packed
         // factor handed over through a workspace), update + applyDelta.
+        // (prepare_step makes the same reservation for slk_step_n: keep the two in step)
         int rc = stage_reserve(f, f->ws_L, (size_t)a.B * pk_size(a.lay.N));
         if (rc) return rc;
         rc = stage_reserve(f, f->ws_DR, ((size_t)a.B * sizeof(int) + sizeof(double) - 1) / sizeof(double));
@@ -297,6 +308,7 @@ static int launch_msckf_inst(slk_filter *f, const KArgs &a0)
         return run_part(a, f->stream);
     }
     if (BIG) {
+        // (prepare_step makes the same reservation for slk_step_n: keep the two in step)
         int rc = stage_reserve(f, f->ws_L, (size_t)a.B * pk_size(a.lay.N));
         if (rc) return rc;
         const size_t ndr = (size_t)a.B * 3 * cv.W;                   // rotation deviations, then one int per filter
@@ -355,6 +367,7 @@ static int launch_msckf_general(slk_filter *f, const KArgs &a0)
     KArgs a = a0;
     if (a.do_update && a.m > MAXM) { g_err = "more than 32 measurement rows per update are not supported"; return SLK_E_UNSUPPORTED; }
     const GenWs w = general_ws(a.lay.N, a.lay.Nq, a.lay.nso3, a.m > 0 ? a.m : 1);
+    // (prepare_step makes the same reservation for slk_step_n: keep the two in step)
     int rc = stage_reserve(f, f->ws_L, (size_t)a.B * w.total);
     if (rc) return rc;
     a.wsL = f->ws_L.p;
@@ -456,6 +469,7 @@ static int launch_usckf_split(slk_filter *f, const KArgs &a0)
         a.wsL = nullptr;
         a.wsfail = nullptr;
     } else {
+        // (prepare_step makes the same reservation for slk_step_n: keep the two in step)
         rc = stage_reserve(f, f->ws_L, (size_t)a.B * pk_size(a.lay.N));
         if (rc) return rc;
         rc = stage_reserve(f, f->ws_DR, ((size_t)a.B * sizeof(int) + sizeof(double) - 1) / sizeof(double));
@@ -500,6 +514,7 @@ static int launch_usckf_wide(slk_filter *f, const KArgs &a0)
 {
     KArgs a = a0;
     const WideWs w = wide_ws(a.lay.N, a.m);
+    // (prepare_step makes the same reservation for slk_step_n: keep the two in step)
     int rc = stage_reserve(f, f->ws_L, (size_t)a.B * w.total);
     if (rc) return rc;
     if (a.do_predict) {
@@ -566,22 +581,31 @@ static int mm_params(int model, int m)
     return model == SLK_MM_FEATURE_PROJ ? (m / 2) * 4 : (model == SLK_MM_POSE_POSITION ? 1 : 0);
 }
 
-static int fill_predict(slk_filter *f, KArgs &a, int model, const double *u, int u_stride,
-                        const double *Q, int q_stride, int where)
+static int check_predict(int model, const double *u, int u_stride, const double *Q, int q_stride)
 {
     if (model != SLK_PM_CONST_VELOCITY && model != SLK_PM_DELTA_POSE && model != SLK_PM_DEAD_RECKON) return SLK_E_INVALID;
     if (!u || !Q) return SLK_E_INVALID;
     int nu = pm_inputs(model);
     if (u_stride != 0 && u_stride < nu) return SLK_E_INVALID;
     if (q_stride != 0 && q_stride < 144) return SLK_E_INVALID;
+    return SLK_OK;
+}
+
+static int fill_predict(slk_filter *f, KArgs &a, int model, const double *u, int u_stride,
+                        const double *Q, int q_stride, int where)
+{
+    int rc0 = check_predict(model, u, u_stride, Q, q_stride);
+    if (rc0) return rc0;
+    int nu = pm_inputs(model);
     a.do_predict = 1; a.pm = model; a.u_stride = u_stride; a.q_stride = q_stride;
     int rc = stage_in(f, f->st_u, u, u_stride ? (size_t)f->B * u_stride : (size_t)nu, where, &a.u);
     if (rc) return rc;
     return stage_in(f, f->st_Q, Q, q_stride ? (size_t)f->B * q_stride : (size_t)144, where, &a.Q);
 }
 
-static int fill_update(slk_filter *f, KArgs &a, int model, const double *params, int p_stride,
-                       const double *z, int m, const double *R, int r_stride, int gate, int where)
+// every check of an update's arguments (host-resident parameters: their pose indices too)
+static int check_update(slk_filter *f, int model, const double *params, int p_stride, const double *z, int m,
+                        const double *R, int r_stride, int where)
 {
     if (m < 1 || !z || !R) return SLK_E_INVALID;
     if (f->lay.kind == SLK_MSCKF && m > MAXM) return SLK_E_INVALID;      // (Usckf: no row limit, slk_usckf_wide.hpp)
@@ -612,6 +636,15 @@ static int fill_update(slk_filter *f, KArgs &a, int model, const double *params,
             } else if (!(row[0] >= 0.0 && row[0] <= maxc)) { g_err = "pose index out of range"; return SLK_E_INVALID; }
         }
     }
+    return SLK_OK;
+}
+
+static int fill_update(slk_filter *f, KArgs &a, int model, const double *params, int p_stride,
+                       const double *z, int m, const double *R, int r_stride, int gate, int where)
+{
+    int rc0 = check_update(f, model, params, p_stride, z, m, R, r_stride, where);
+    if (rc0) return rc0;
+    int np = mm_params(model, m);
     a.do_update = 1; a.mm = model; a.m = m; a.gate = gate; a.mp_stride = p_stride; a.r_stride = r_stride;
     int rc = np ? stage_in(f, f->st_mp, params, p_stride ? (size_t)f->B * p_stride : (size_t)np, where, &a.mp) : SLK_OK;
     if (rc) return rc;
@@ -1281,6 +1314,171 @@ int slk_sample_states(slk_filter *f, const double *noise, int S, double *out, in
         HIPCHECK(hipStreamSynchronize(f->stream));
     }
     return SLK_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------- multi-step trajectories (slk_step_n)
+// What the launch of one step at this shape (slk_step's route, launch()) reserves and checks before its kernels: made
+// once, before the first launch of a trajectory, so that no step after the first can fail a reservation.
+static int prepare_step(slk_filter *f, const KArgs &a)
+{
+    const Lay &L = f->lay;
+    const size_t B = (size_t)f->B;
+    const size_t nfail = (B * sizeof(int) + sizeof(double) - 1) / sizeof(double);
+    const int NT = (L.N + 15) / 16;
+    int rc = SLK_OK;
+    if (L.kind == SLK_MSCKF) {
+        if (NT > 13) return stage_reserve(f, f->ws_L, B * general_ws(L.N, L.Nq, L.nso3, a.m).total);
+        const int NTI = NT <= 6 ? NT : (NT <= 8 ? 8 : (NT <= 10 ? 10 : 13));     // the instantiation launch_msckf picks
+        const bool BIG = NTI > 4;
+        const Carve cv = carve_step(L, a.m, NTI, BIG, a.rebuild_prec);
+        rc = ensure_rtab(f, L, cv.W);
+        if (rc) return rc;
+        if (NT >= 3) {
+            rc = stage_reserve(f, f->ws_L, B * pk_size(L.N));
+            if (rc) return rc;
+            rc = stage_reserve(f, f->ws_DR, (BIG ? B * 3 * cv.W : 0) + nfail);
+            if (rc) return rc;
+        }
+        if (BIG && (size_t)cv.total * sizeof(double) > 160 * 1024) {
+            g_err = "state too large for the LDS-resident kernel"; return SLK_E_UNSUPPORTED;
+        }
+        return SLK_OK;
+    }
+    if (a.m > MAXM || L.N > 96) return stage_reserve(f, f->ws_L, B * wide_ws(L.N, a.m).total);
+    if (L.N <= 48) {
+        const bool fused_factor = L.nfk == 3 && L.nfkl == 9 && a.m == 3 && a.mm == SLK_MM_VO_RELATIVE && a.gate <= 9;
+        if (fused_factor) return SLK_OK;
+        rc = stage_reserve(f, f->ws_L, B * pk_size(L.N));
+        if (rc) return rc;
+        return stage_reserve(f, f->ws_DR, nfail);
+    }
+    if ((size_t)carve_usckf(L.N, L.Nq, a.m, NT).total * sizeof(double) > 160 * 1024) {
+        g_err = "state too large for the LDS-resident kernel"; return SLK_E_UNSUPPORTED;
+    }
+    return SLK_OK;
+}
+
+extern "C" {
+
+int slk_step_n(slk_filter *f, const slk_traj *t, int where)
+{
+    if (!f || !t || t->T < 1 || t->mmodel == SLK_MODEL_EXTERNAL) return SLK_E_INVALID;
+    if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
+    const int T = t->T, m = t->m;
+    const size_t B = (size_t)f->B, Nq = (size_t)f->lay.Nq;
+    // ---- every check, before anything is reserved or launched
+    int rc = check_predict(t->pmodel, t->u, t->u_stride, t->Q, t->q_stride);
+    if (rc) return rc;
+    rc = check_update(f, t->mmodel, t->params, t->p_stride, t->z, m, t->R, t->r_stride, SLK_DEVICE);
+    if (rc) return rc;
+    const int np = mm_params(t->mmodel, m);
+    // one step's block of each input (what slk_step reads), and what all T steps read
+    const size_t bu = t->u_stride ? B * t->u_stride : (size_t)pm_inputs(t->pmodel);
+    const size_t bq = t->q_stride ? B * t->q_stride : (size_t)144;
+    const size_t bp = np ? (t->p_stride ? B * t->p_stride : (size_t)np) : 0;
+    const size_t bz = B * m;
+    const size_t br = t->r_stride ? B * t->r_stride : (size_t)m * m;
+    auto short_ts = [](long long ts, size_t blk) { return ts < 0 || (ts != 0 && (size_t)ts < blk); };
+    auto span = [T](long long ts, size_t blk) { return ts ? (size_t)(T - 1) * (size_t)ts + blk : blk; };
+    if (short_ts(t->u_tstride, bu) || short_ts(t->q_tstride, bq) || (np && short_ts(t->p_tstride, bp))
+        || short_ts(t->z_tstride, bz) || short_ts(t->r_tstride, br)) {
+        g_err = "slk_step_n: a nonzero per-step stride is shorter than one step's block";
+        return SLK_E_INVALID;
+    }
+    const bool want_nees = t->nees_hist != nullptr;
+    if (want_nees) {
+        if (!t->truth || t->nees_t0 < 0 || t->nees_n < 1 || t->nees_n > f->lay.N - t->nees_t0) return SLK_E_INVALID;
+        if (short_ts(t->truth_tstride, B * Nq)) return SLK_E_INVALID;
+    }
+    if (np && where == SLK_HOST) {                              // the pose indices of every step's parameters
+        const int nblk = t->p_tstride ? T : 1;
+        for (int s = 0; s < nblk; ++s) {
+            rc = check_update(f, t->mmodel, t->params + (size_t)s * t->p_tstride, t->p_stride, t->z, m, t->R, t->r_stride,
+                              SLK_HOST);
+            if (rc) return rc;
+        }
+    }
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    KArgs a;
+    base_args(f, a);
+    a.do_predict = 1; a.pm = t->pmodel; a.u_stride = t->u_stride; a.q_stride = t->q_stride;
+    a.do_update = 1; a.mm = t->mmodel; a.m = m; a.gate = t->gate; a.mp_stride = t->p_stride; a.r_stride = t->r_stride;
+    // ---- every reservation, before the first launch
+    const size_t su = span(t->u_tstride, bu), sq = span(t->q_tstride, bq), sp = np ? span(t->p_tstride, bp) : 0;
+    const size_t sz = span(t->z_tstride, bz), sr = span(t->r_tstride, br);
+    const size_t sth = want_nees ? span(t->truth_tstride, B * Nq) : 0;
+    const size_t nmean = t->mean_hist ? (size_t)T * B * Nq : 0, nnees = want_nees ? (size_t)T * B : 0;
+    const size_t nout = t->outliers_hist ? ((size_t)T * B * sizeof(unsigned) + sizeof(double) - 1) / sizeof(double) : 0;
+    if (where == SLK_HOST) {
+        Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_truth, &f->st_rec};
+        const size_t n[] = {su, sq, sp, sz, sr, sth, nmean + nnees + nout};
+        for (int i = 0; i < 7; ++i) if (n[i]) { rc = stage_reserve(f, *st[i], n[i]); if (rc) return rc; }
+    }
+    rc = prepare_step(f, a);
+    if (rc) return rc;
+    const bool nees_rows = want_nees && t->nees_n <= NEES_ROWS_MAX;     // the one-wave record kernel: no workspace
+    if (want_nees && !nees_rows) { rc = stage_reserve(f, f->ws_cons, B * consistency_ws(t->nees_n).total); if (rc) return rc; }
+#ifdef SLK_DEV_N60
+    g_err = "development build: no trajectory route"; return SLK_E_UNSUPPORTED;
+#else
+    // ---- one upload of each input for all T steps (host route)
+    const double *du = t->u, *dq = t->Q, *dp = np ? t->params : nullptr, *dz = t->z, *dr = t->R, *dth = t->truth;
+    double *dmean = t->mean_hist, *dnees = t->nees_hist;
+    unsigned *dout = t->outliers_hist;
+    if (where == SLK_HOST) {
+        auto up = [&](Stage &s, const double *src, size_t n, const double **out) -> int {
+            if (!n) return SLK_OK;
+            HIPCHECK(hipMemcpyAsync(s.p, src, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
+            *out = s.p;
+            return SLK_OK;
+        };
+        if ((rc = up(f->st_u, t->u, su, &du)) || (rc = up(f->st_Q, t->Q, sq, &dq)) || (rc = up(f->st_mp, t->params, sp, &dp))
+            || (rc = up(f->st_z, t->z, sz, &dz)) || (rc = up(f->st_R, t->R, sr, &dr)) || (rc = up(f->st_truth, t->truth, sth, &dth)))
+            return rc;
+        dmean = t->mean_hist ? f->st_rec.p : nullptr;
+        dnees = want_nees ? f->st_rec.p + nmean : nullptr;
+        dout = t->outliers_hist ? reinterpret_cast<unsigned *>(f->st_rec.p + nmean + nnees) : nullptr;
+    }
+    a.u = du; a.Q = dq; a.mp = dp; a.z = dz; a.R = dr;
+    // slk_step's launch() per step on the inputs of that step (its route, its bookkeeping), then the records
+    for (int s = 0; s < T; ++s) {
+        KArgs as = a;
+        as.u = du + (size_t)s * t->u_tstride;
+        as.Q = dq + (size_t)s * t->q_tstride;
+        as.mp = dp ? dp + (size_t)s * t->p_tstride : nullptr;
+        as.z = dz + (size_t)s * t->z_tstride;
+        as.R = dr + (size_t)s * t->r_tstride;
+        rc = launch(f, as);
+        if (rc) return rc;
+        if (dmean)
+            HIPCHECK(hipMemcpyAsync(dmean + (size_t)s * B * Nq, f->d_mean, B * Nq * sizeof(double), hipMemcpyDeviceToDevice,
+                                    f->stream));
+        if (dout)
+            HIPCHECK(hipMemcpyAsync(dout + (size_t)s * B, f->d_outliers, B * sizeof(unsigned), hipMemcpyDeviceToDevice,
+                                    f->stream));
+        if (nees_rows) {
+            hipLaunchKernelGGL(nees_rows_kernel, dim3(f->B), dim3(64), 0, f->stream, f->lay, (const double *)f->d_mean,
+                               (const double *)f->d_P, dth + (size_t)s * t->truth_tstride, t->nees_t0, t->nees_n,
+                               dnees + (size_t)s * B);
+            HIPCHECK(hipGetLastError());
+        } else if (want_nees) {
+            hipLaunchKernelGGL(nees_kernel, dim3(f->B), dim3(256), 0, f->stream, f->lay, (const double *)f->d_mean,
+                               (const double *)f->d_P, dth + (size_t)s * t->truth_tstride, t->nees_t0, t->nees_n,
+                               dnees + (size_t)s * B, (double *)nullptr, f->ws_cons.p);
+            HIPCHECK(hipGetLastError());
+        }
+    }
+    if (where == SLK_HOST) {                                    // one download of the records
+        if (t->mean_hist) HIPCHECK(hipMemcpyAsync(t->mean_hist, dmean, nmean * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (want_nees) HIPCHECK(hipMemcpyAsync(t->nees_hist, dnees, nnees * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (t->outliers_hist)
+            HIPCHECK(hipMemcpyAsync(t->outliers_hist, dout, (size_t)T * B * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream));
+        HIPCHECK(hipStreamSynchronize(f->stream));
+    }
+    return SLK_OK;
+#endif
 }
 
 struct slk_adaptive {

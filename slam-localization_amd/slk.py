@@ -33,7 +33,7 @@ EXPORTS = [
     "slk_selftest_mfma", "slk_set_rebuild_precision", "slk_dead_reckon", "slk_msckf_clone_pose", "slk_msckf_drop_clone", "slk_update_ekf",
     "slk_check_sigma_points", "slk_update_innovation", "slk_update_selected", "slk_transform_compose",
     "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix", "slk_nees",
-    "slk_sample_states",
+    "slk_sample_states", "slk_step_n",
 ]
 
 
@@ -44,6 +44,20 @@ class SlkError(RuntimeError):
 class Config(C.Structure):
     _fields_ = [("kind", C.c_int), ("batch", C.c_int), ("device", C.c_int), ("n_clones", C.c_int),
                 ("n_featuresk", C.c_int), ("n_featuresk_l", C.c_int), ("stream", C.c_void_p)]
+
+
+class Traj(C.Structure):
+    """struct slk_traj of include/slk.h"""
+    _fields_ = [("T", C.c_int),
+                ("pmodel", C.c_int), ("u", C.c_void_p), ("u_stride", C.c_int), ("u_tstride", C.c_longlong),
+                ("Q", C.c_void_p), ("q_stride", C.c_int), ("q_tstride", C.c_longlong),
+                ("mmodel", C.c_int), ("params", C.c_void_p), ("p_stride", C.c_int), ("p_tstride", C.c_longlong),
+                ("z", C.c_void_p), ("m", C.c_int), ("z_tstride", C.c_longlong),
+                ("R", C.c_void_p), ("r_stride", C.c_int), ("r_tstride", C.c_longlong),
+                ("gate", C.c_int),
+                ("mean_hist", C.c_void_p), ("outliers_hist", C.c_void_p),
+                ("truth", C.c_void_p), ("truth_tstride", C.c_longlong), ("nees_t0", C.c_int), ("nees_n", C.c_int),
+                ("nees_hist", C.c_void_p)]
 
 
 _lib = None
@@ -101,6 +115,7 @@ def load_library(path=None):
     lib.slk_adaptive_matrix.argtypes = [vp, ip, vp, vp, vp, vp, vp, ip, vp, ip]
     lib.slk_nees.argtypes = [vp, vp, ip, ip, vp, vp, ip]
     lib.slk_sample_states.argtypes = [vp, vp, ip, vp, ip]
+    lib.slk_step_n.argtypes = [vp, C.POINTER(Traj), ip]
     if path is None:
         _lib = lib
     return lib
@@ -172,6 +187,32 @@ def _mat(M, B, n):
     assert M.shape == (B, n, n), (M.shape, B, n)
     a = np.ascontiguousarray(np.transpose(M, (0, 2, 1)))
     return _Arg(a.ctypes.data, n * n, HOST, a)
+
+
+def _steps(a, T, B, width, name, exact=False, per_filter=False):
+    """A per-step input with a leading T axis: (pointer, per-filter stride, per-step stride, where, keep-alive).
+    [T, w] = one shared row per step, [T, B, w] = per-filter rows (per_filter: only those); w >= width (exact: w ==
+    width).  A stride of 0 on the T axis (np.broadcast_to, torch expand) shares one block over every step without a
+    copy.  The C ABI reads whole blocks of these sizes, so every shape is checked here."""
+    if a is None:
+        return None
+    shape = tuple(a.shape)
+    ok = len(shape) == 3 or (len(shape) == 2 and not per_filter)
+    ok = ok and shape[0] == T and (len(shape) == 2 or shape[1] == B)
+    ok = ok and (shape[-1] == width if exact else shape[-1] >= width)
+    if not ok:
+        want = f"[{T}, {B}, {width}]" if per_filter else f"[{T}, ({B},) {'' if exact else '>='}{width}]"
+        raise SlkError(f"step_n: {name} must be {want}, got {shape}")
+    if _is_dev(a):
+        if not a[0].is_contiguous() or str(a.dtype) != "torch.float64":
+            raise SlkError(f"step_n: {name} must be a float64 tensor with contiguous steps")
+        return (a.data_ptr(), int(a.stride(1)) if a.dim() == 3 else 0, int(a.stride(0)), DEVICE if a.is_cuda else HOST, a)
+    a = np.asarray(a, dtype=np.float64)
+    if a.strides[0] == 0:
+        blk = np.ascontiguousarray(a[0])
+        return (blk.ctypes.data, a.shape[2] if a.ndim == 3 else 0, 0, HOST, blk)
+    a = np.ascontiguousarray(a)
+    return (a.ctypes.data, a.shape[2] if a.ndim == 3 else 0, int(np.prod(a.shape[1:])), HOST, a)
 
 
 def _where(*args):
@@ -304,6 +345,65 @@ class _FilterBatch:
         _check(self._lib.slk_step(self._h, pmodel, ua.ptr, ua.stride, qa.ptr, qa.stride, mmodel, pa.ptr, pa.stride,
                                   za.ptr, m, ra.ptr, ra.stride, self._default_gate(gate), _where(ua, qa, pa, za, ra)),
                "slk_step")
+
+    def step_n(self, pmodel, u, Q, z, mmodel, params, R, gate=None, truth=None, nees_range=None, record_mean=False,
+               record_outliers=False):
+        """T fused steps in one call (slk_step_n): the same results as T calls of step() with the inputs of each step.
+        u [T, B, nu] or [T, nu], z [T, B, m], params [T, B, np] or [T, np] (or None), truth [T, B, Nq]: a leading T axis
+        always (a stride of 0 there, np.broadcast_to / torch expand, shares one block over all steps); Q and R have the
+        shapes step() takes and are shared over the steps.  Records: record_mean -> "mean" [T, B, Nq] (the mean after
+        each step), record_outliers -> "outliers" [T, B], truth -> "nees" [T, B] (nees(truth[t], t0, n) after step t,
+        nees_range = (t0, n), default the whole state).  numpy in -> host route, numpy records; torch device tensors in
+        -> device route, device tensors out."""
+        T = int(z.shape[0])
+        m = int(z.shape[-1])
+        B = self.B
+        ua = _steps(u, T, B, 7 if pmodel == PM_CONST_VELOCITY else 13, "u")
+        za = _steps(z, T, B, m, "z", exact=True, per_filter=True)
+        npar = _np(mmodel, m)
+        pa = _steps(params, T, B, npar, "params") if npar else None
+        ta = _steps(truth, T, B, self.Nq, "truth", exact=True, per_filter=True)
+        qa, ra = _mat(Q, B, 12), _mat(R, B, m)
+        parts = [x for x in (ua, za, pa, ta) if x is not None]
+        where = _where(qa, ra, *[_Arg(x[0], x[1], x[3], x[4]) for x in parts])
+        t0, n = (0, self.N) if nees_range is None else (int(nees_range[0]), int(nees_range[1]))
+        tr = Traj()
+        tr.T = T
+        tr.pmodel, tr.u, tr.u_stride, tr.u_tstride = pmodel, ua[0], ua[1], ua[2]
+        tr.Q, tr.q_stride, tr.q_tstride = qa.ptr, qa.stride, 0
+        tr.mmodel = mmodel
+        if pa is not None:
+            tr.params, tr.p_stride, tr.p_tstride = pa[0], pa[1], pa[2]
+        tr.z, tr.m, tr.z_tstride = za[0], m, za[2]
+        tr.R, tr.r_stride, tr.r_tstride = ra.ptr, ra.stride, 0
+        tr.gate = self._default_gate(gate)
+        out = {}
+        if where == DEVICE:
+            import torch
+            dev = z.device
+            torch.cuda.current_stream(dev).synchronize()      # (the handle's stream does not wait for torch's)
+            if record_mean:
+                out["mean"] = torch.empty((T, B, self.Nq), dtype=torch.float64, device=dev)
+            if record_outliers:
+                out["outliers"] = torch.empty((T, B), dtype=torch.uint32, device=dev)
+            if truth is not None:
+                out["nees"] = torch.empty((T, B), dtype=torch.float64, device=dev)
+            ptr = {k: v.data_ptr() for k, v in out.items()}
+        else:
+            if record_mean:
+                out["mean"] = np.empty((T, B, self.Nq))
+            if record_outliers:
+                out["outliers"] = np.empty((T, B), dtype=np.uint32)
+            if truth is not None:
+                out["nees"] = np.empty((T, B))
+            ptr = {k: v.ctypes.data for k, v in out.items()}
+        tr.mean_hist, tr.outliers_hist, tr.nees_hist = ptr.get("mean"), ptr.get("outliers"), ptr.get("nees")
+        if ta is not None:
+            tr.truth, tr.truth_tstride, tr.nees_t0, tr.nees_n = ta[0], ta[2], t0, n
+        _check(self._lib.slk_step_n(self._h, C.byref(tr), where), "slk_step_n")
+        if where == DEVICE:
+            self.sync()                                        # torch may read the records on any stream
+        return out
 
     # ---- Tier B: opaque host functors (the reference's boost::bind form)
     def predict_sigma_points(self):
