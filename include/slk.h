@@ -261,6 +261,17 @@ typedef struct slk_traj {
     double   *nees_hist;      /* [T][B]: slk_nees(truth_t, nees_t0, nees_n) after step t (needs truth) */
 } slk_traj;
 int slk_step_n(slk_filter *f, const slk_traj *t, int where);
+/* ---- sliding-window trajectories: slk_step_n with a window slide after chosen steps (the reference has no such call:
+ *      its callers push / pop muState().sensorsk and setPk between updates).  slide [T] is a HOST array in both routes
+ *      (`where` refers to the trajectory's data as in slk_step_n): slide[t] = -1 leaves the window as it is after step
+ *      t, slide[t] = d in 0 .. k - 1 runs slk_msckf_slide(f, d) after step t.  slide == NULL is exactly slk_step_n.
+ *      The mean, P (as slk_get_state reads it), the status bits, the outlier counts and every record are bit-identical
+ *      to a loop of T x (slk_step, then slk_msckf_drop_clone(d_t) + slk_msckf_clone_pose when d_t >= 0); the records
+ *      of step t are taken AFTER its slide.  Every schedule entry is checked with slk_step_n's checks, and the second
+ *      state buffer pair is reserved, before the first launch: an entry outside -1 .. k - 1, or a schedule on a Usckf
+ *      handle, is SLK_E_INVALID and leaves the filter untouched.  The schedule is a separate argument: slk_traj and
+ *      its size are those of slk_step_n. ---- */
+int slk_step_n_slide(slk_filter *f, const slk_traj *t, const int *slide, int where);
 
 /* ---- Tier B (opaque host functors, the reference's boost::bind form:
  *      UsckfUnitTest.cpp:246,284; MsckfUnitTest.cpp:200-205).  The library draws the sigma
@@ -285,6 +296,14 @@ int slk_msckf_resize(slk_filter *f, int n_clones);
  *     the pose's (J P J^T, J = [I; E_pose]); drop_clone removes clone `index` (0 = oldest) with its 6 rows / columns. */
 int slk_msckf_clone_pose(slk_filter *f);
 int slk_msckf_drop_clone(slk_filter *f, int index);
+/* One slide of the window, k unchanged: drop clone `index` (0 = oldest), then clone the current pose as the newest --
+ *     bit for bit what slk_msckf_drop_clone(f, index) followed by slk_msckf_clone_pose(f) give, in one launch and with no
+ *     pass that completes P first.  A covariance whose strict upper triangle is stale (after the exact-shape steps) is
+ *     read and written as its lower triangle (N (N + 1) / 2 doubles each way per filter) and stays lower-only, to be
+ *     completed on demand like after those steps; a complete one is gathered whole.  The mean and P move to the
+ *     handle's second buffer pair (slk_mean_device_ptr / slk_cov_device_ptr change, as after clone / drop).
+ *     SLK_E_INVALID, the filter untouched: a Usckf handle, k = 0, or an index outside 0 .. k - 1. */
+int slk_msckf_slide(slk_filter *f, int index);
 
 /* ---- checkSigmaPoints(): Msckf.hpp:819-839 (Usckf.hpp:769-789 is the same self test).  Re-draws the sigma points of
  *      (mu_state, Pk), takes their manifold mean and covariance on the device and reports per filter

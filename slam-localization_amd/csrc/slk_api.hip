@@ -695,6 +695,58 @@ __global__ void msckf_window_kernel(const double *mean, const double *P, double 
     }
 }
 
+// One slide of the window, k unchanged: drop clone d, then append a clone of the current pose -- what op 2 (d) and then
+// op 1 of msckf_window_kernel give, in one gather.  New tangent index t comes from src(t): the identity on the state and
+// on the clones before d, the clones after d one block down, the new (last) clone block from the pose (tangent 0..5).
+// lower = 1 (a lower-only covariance, slk_filter::upper_stale): the lower triangle and the diagonal are read and written,
+// P_new(r, c) = P(max(src r, src c), min(...)); the columns are taken in pairs (c, N - 1 - c) of N + 1 elements
+// (N = 12 + 6k is even), so each pair is two contiguous runs.  lower = 0: the whole matrix, element for element.
+// grid (B, chunks of SLIDE_CHUNK elements), 256 threads, SLIDE_UNROLL independent loads in flight per thread; the mean
+// is moved by the chunk-0 workgroup of each filter.
+constexpr int SLIDE_UNROLL = 8, SLIDE_CHUNK = 256 * SLIDE_UNROLL;
+
+__global__ __launch_bounds__(256) void msckf_slide_kernel(const double *__restrict__ mean, const double *__restrict__ P,
+                                                          double *__restrict__ nmean, double *__restrict__ nP, int k, int d,
+                                                          int lower)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int N = 12 + 6 * k, Nq = 13 + 7 * k, last = N - 6, cut = 12 + 6 * d;
+    const double *Pb = P + (size_t)b * N * N;
+    double *Po = nP + (size_t)b * N * N;
+    if (blockIdx.y == 0) {
+        const double *m = mean + (size_t)b * Nq;
+        double *mo = nmean + (size_t)b * Nq;
+        for (int e = tid; e < Nq; e += 256)
+            mo[e] = m[e >= Nq - 7 ? e - (Nq - 7) : (e < 13 + 7 * d ? e : e + 7)];    // (pos[3] quat[4] sit at 0..6)
+    }
+    auto src = [&](int t) { return t >= last ? t - last : (t < cut ? t : t + 6); };
+    const int total = lower ? (N / 2) * (N + 1) : N * N;
+    const int e0 = blockIdx.y * SLIDE_CHUNK + tid;
+    int dst[SLIDE_UNROLL];
+    double v[SLIDE_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SLIDE_UNROLL; ++u) {
+        const int e = e0 + 256 * u;
+        dst[u] = -1;
+        if (e >= total) continue;
+        int r, c;
+        if (lower) {
+            const int q = e / (N + 1), t = e - q * (N + 1);
+            if (t < N - q) { c = q; r = q + t; }                     // column q, rows q .. N - 1
+            else { c = N - 1 - q; r = c + (t - (N - q)); }           // column N - 1 - q, rows N - 1 - q .. N - 1
+        } else {
+            c = e / N; r = e - c * N;
+        }
+        const int sr = src(r), sc = src(c);
+        const int i = lower ? max(sr, sc) : sr, j = lower ? min(sr, sc) : sc;
+        v[u] = Pb[i + (size_t)j * N];
+        dst[u] = r + c * N;
+    }
+#pragma unroll
+    for (int u = 0; u < SLIDE_UNROLL; ++u)
+        if (dst[u] >= 0) Po[dst[u]] = v[u];
+}
+
 // checkSigmaPoints (Msckf.hpp:819-839), second half: compare the re-drawn mean / covariance with the filter's own.
 // One workgroup per filter; res [2][B] = max |Pktest - Pk|, |mu_state [-] muX|.
 __global__ void check_compare_kernel(Lay L, const double *mean, const double *P, const double *mean2, const double *P2, int B,
@@ -1205,6 +1257,45 @@ static int msckf_window_op(slk_filter *f, int op, int idx)
 int slk_msckf_clone_pose(slk_filter *f) { return msckf_window_op(f, 1, 0); }
 int slk_msckf_drop_clone(slk_filter *f, int index) { return msckf_window_op(f, 2, index); }
 
+// The second buffer pair of a slide (the state keeps its size), and the one limit of its launch shape.
+static long long slide_chunks(const slk_filter *f, int lower)
+{
+    const int N = f->lay.N;
+    const long long total = lower ? (long long)(N / 2) * (N + 1) : (long long)N * N;
+    return (total + SLIDE_CHUNK - 1) / SLIDE_CHUNK;
+}
+
+static int reserve_slide(slk_filter *f)
+{
+    if (slide_chunks(f, 0) > 65535) { g_err = "slide: state too large for the slide kernel's grid"; return SLK_E_UNSUPPORTED; }
+    const size_t B = (size_t)f->B;
+    return reserve_alt(f, B * f->lay.Nq, B * (size_t)f->lay.N * f->lay.N);
+}
+
+// One slide (msckf_slide_kernel) into the second buffer pair, then the pairs swap; the caller has checked the index and
+// made the reservation (reserve_slide).  The covariance stays as complete as it was: a lower-only one (upper_stale) is
+// slid as its lower triangle and stays lower-only, a complete one is gathered whole -- bit for bit what drop_clone +
+// clone_pose give either way, with no mirror pass first.
+static int launch_slide(slk_filter *f, int index)
+{
+    const int lower = f->upper_stale ? 1 : 0;
+    const long long chunks = slide_chunks(f, lower);          // (<= 65535: reserve_slide)
+    hipLaunchKernelGGL(msckf_slide_kernel, dim3(f->B, (unsigned)chunks), dim3(256), 0, f->stream, (const double *)f->d_mean,
+                       (const double *)f->d_P, f->d_mean_alt, f->d_P_alt, f->lay.k, index, lower);
+    HIPCHECK(hipGetLastError());
+    swap_state_buffers(f);
+    return SLK_OK;
+}
+
+int slk_msckf_slide(slk_filter *f, int index)
+{
+    if (!f || f->lay.kind != SLK_MSCKF || f->lay.k < 1 || index < 0 || index >= f->lay.k) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    int rc = reserve_slide(f);
+    if (rc) return rc;
+    return launch_slide(f, index);
+}
+
 int slk_msckf_resize(slk_filter *f, int n_clones)
 {
     if (!f || f->lay.kind != SLK_MSCKF || n_clones < 0) return SLK_E_INVALID;
@@ -1362,13 +1453,23 @@ static int prepare_step(slk_filter *f, const KArgs &a)
 
 extern "C" {
 
-int slk_step_n(slk_filter *f, const slk_traj *t, int where)
+// slk_step_n and slk_step_n_slide: slide == NULL is slk_step_n; slide[t] >= 0 slides the window after step t, before
+// that step's records.
+static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
 {
     if (!f || !t || t->T < 1 || t->mmodel == SLK_MODEL_EXTERNAL) return SLK_E_INVALID;
     if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
     const int T = t->T, m = t->m;
     const size_t B = (size_t)f->B, Nq = (size_t)f->lay.Nq;
     // ---- every check, before anything is reserved or launched
+    bool any_slide = false;
+    if (slide) {                                                // (host memory in both routes)
+        if (f->lay.kind != SLK_MSCKF) return SLK_E_INVALID;
+        for (int s = 0; s < T; ++s) {
+            if (slide[s] < -1 || slide[s] >= f->lay.k) return SLK_E_INVALID;
+            any_slide |= slide[s] >= 0;
+        }
+    }
     int rc = check_predict(t->pmodel, t->u, t->u_stride, t->Q, t->q_stride);
     if (rc) return rc;
     rc = check_update(f, t->mmodel, t->params, t->p_stride, t->z, m, t->R, t->r_stride, SLK_DEVICE);
@@ -1418,6 +1519,7 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where)
     }
     rc = prepare_step(f, a);
     if (rc) return rc;
+    if (any_slide) { rc = reserve_slide(f); if (rc) return rc; }
     const bool nees_rows = want_nees && t->nees_n <= NEES_ROWS_MAX;     // the one-wave record kernel: no workspace
     if (want_nees && !nees_rows) { rc = stage_reserve(f, f->ws_cons, B * consistency_ws(t->nees_n).total); if (rc) return rc; }
 #ifdef SLK_DEV_N60
@@ -1445,6 +1547,7 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where)
     // slk_step's launch() per step on the inputs of that step (its route, its bookkeeping), then the records
     for (int s = 0; s < T; ++s) {
         KArgs as = a;
+        as.mean = f->d_mean; as.P = f->d_P;                    // (a slide swaps the buffer pairs)
         as.u = du + (size_t)s * t->u_tstride;
         as.Q = dq + (size_t)s * t->q_tstride;
         as.mp = dp ? dp + (size_t)s * t->p_tstride : nullptr;
@@ -1452,6 +1555,7 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where)
         as.R = dr + (size_t)s * t->r_tstride;
         rc = launch(f, as);
         if (rc) return rc;
+        if (slide && slide[s] >= 0) { rc = launch_slide(f, slide[s]); if (rc) return rc; }
         if (dmean)
             HIPCHECK(hipMemcpyAsync(dmean + (size_t)s * B * Nq, f->d_mean, B * Nq * sizeof(double), hipMemcpyDeviceToDevice,
                                     f->stream));
@@ -1480,6 +1584,10 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where)
     return SLK_OK;
 #endif
 }
+
+int slk_step_n(slk_filter *f, const slk_traj *t, int where) { return step_n(f, t, nullptr, where); }
+
+int slk_step_n_slide(slk_filter *f, const slk_traj *t, const int *slide, int where) { return step_n(f, t, slide, where); }
 
 struct slk_adaptive {
     int B, device;

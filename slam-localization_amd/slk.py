@@ -33,7 +33,7 @@ EXPORTS = [
     "slk_selftest_mfma", "slk_set_rebuild_precision", "slk_dead_reckon", "slk_msckf_clone_pose", "slk_msckf_drop_clone", "slk_update_ekf",
     "slk_check_sigma_points", "slk_update_innovation", "slk_update_selected", "slk_transform_compose",
     "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix", "slk_nees",
-    "slk_sample_states", "slk_step_n",
+    "slk_sample_states", "slk_step_n", "slk_step_n_slide", "slk_msckf_slide",
 ]
 
 
@@ -116,6 +116,8 @@ def load_library(path=None):
     lib.slk_nees.argtypes = [vp, vp, ip, ip, vp, vp, ip]
     lib.slk_sample_states.argtypes = [vp, vp, ip, vp, ip]
     lib.slk_step_n.argtypes = [vp, C.POINTER(Traj), ip]
+    lib.slk_step_n_slide.argtypes = [vp, C.POINTER(Traj), vp, ip]
+    lib.slk_msckf_slide.argtypes = [vp, ip]
     if path is None:
         _lib = lib
     return lib
@@ -285,6 +287,11 @@ class _FilterBatch:
         return np.ascontiguousarray(np.transpose(p, (0, 2, 1)))
 
     def device_pointers(self):
+        """(mean, P) device addresses of the resident state, for zero-copy callers.  Both change after clone_pose,
+        drop_clone, slide and a Usckf setMeasurement (the state moves to the handle's second buffer pair): ask again
+        after each.  The exact-shape Msckf steps and a slide of their result leave the strict upper triangle of P stale;
+        slk_cov_device_ptr, called here, completes it on the handle's stream, so call device_pointers() again after
+        every step or slide before reading the upper triangle through the pointer."""
         return self._lib.slk_mean_device_ptr(self._h), self._lib.slk_cov_device_ptr(self._h)
 
     def status(self):
@@ -347,17 +354,29 @@ class _FilterBatch:
                "slk_step")
 
     def step_n(self, pmodel, u, Q, z, mmodel, params, R, gate=None, truth=None, nees_range=None, record_mean=False,
-               record_outliers=False):
+               record_outliers=False, slide=None):
         """T fused steps in one call (slk_step_n): the same results as T calls of step() with the inputs of each step.
         u [T, B, nu] or [T, nu], z [T, B, m], params [T, B, np] or [T, np] (or None), truth [T, B, Nq]: a leading T axis
         always (a stride of 0 there, np.broadcast_to / torch expand, shares one block over all steps); Q and R have the
         shapes step() takes and are shared over the steps.  Records: record_mean -> "mean" [T, B, Nq] (the mean after
         each step), record_outliers -> "outliers" [T, B], truth -> "nees" [T, B] (nees(truth[t], t0, n) after step t,
         nees_range = (t0, n), default the whole state).  numpy in -> host route, numpy records; torch device tensors in
-        -> device route, device tensors out."""
+        -> device route, device tensors out.
+        slide (slk_step_n_slide): an int d slides the window after every step (drop clone d, clone the current pose),
+        or a length-T sequence with -1 (no slide after that step) or d; the records of a step are taken after its
+        slide.  The results are those of step() followed by drop_clone(d) + clone_pose() where d >= 0."""
         T = int(z.shape[0])
         m = int(z.shape[-1])
         B = self.B
+        sched = None
+        if slide is not None:
+            if np.ndim(slide) == 0:
+                sched = np.full(T, int(slide), dtype=np.int32)
+            else:
+                sched = np.asarray(slide)
+                if sched.ndim != 1 or sched.shape[0] != T or not np.issubdtype(sched.dtype, np.integer):
+                    raise SlkError(f"step_n: slide must be an int or {T} integers, got {sched.dtype} {sched.shape}")
+                sched = np.ascontiguousarray(sched, dtype=np.int32)
         ua = _steps(u, T, B, 7 if pmodel == PM_CONST_VELOCITY else 13, "u")
         za = _steps(z, T, B, m, "z", exact=True, per_filter=True)
         npar = _np(mmodel, m)
@@ -400,7 +419,10 @@ class _FilterBatch:
         tr.mean_hist, tr.outliers_hist, tr.nees_hist = ptr.get("mean"), ptr.get("outliers"), ptr.get("nees")
         if ta is not None:
             tr.truth, tr.truth_tstride, tr.nees_t0, tr.nees_n = ta[0], ta[2], t0, n
-        _check(self._lib.slk_step_n(self._h, C.byref(tr), where), "slk_step_n")
+        if sched is None:
+            _check(self._lib.slk_step_n(self._h, C.byref(tr), where), "slk_step_n")
+        else:
+            _check(self._lib.slk_step_n_slide(self._h, C.byref(tr), sched.ctypes.data, where), "slk_step_n_slide")
         if where == DEVICE:
             self.sync()                                        # torch may read the records on any stream
         return out
@@ -608,6 +630,10 @@ class Msckf(_FilterBatch):
     def drop_clone(self, index=0):
         """Device-side erase of clone `index` (0 = oldest) with its covariance rows / columns."""
         _check(self._lib.slk_msckf_drop_clone(self._h, int(index)), "slk_msckf_drop_clone")
+
+    def slide(self, index=0):
+        """One slide of the window, k unchanged: drop_clone(index) + clone_pose() in one launch, bit for bit."""
+        _check(self._lib.slk_msckf_slide(self._h, int(index)), "slk_msckf_slide")
 
 
 class Usckf(_FilterBatch):
