@@ -242,10 +242,11 @@ class Msckf:
         return outliers
 
 
-def msckf_update_ekf(filt, z, zmean, H, R, gate=True):
+def msckf_update_ekf(filt, z, zmean, H, R, gate=True, decisions=None):
     """Msckf EKF update (Msckf.hpp:284-349) with numpy/LAPACK: removeOutliers :756-789 (the information matrix is
     inverted once and indexed with the running block number), reduceDimension :791-816 through numpy's Householder
-    QR (LAPACK dgeqrf uses the same reflector convention as Eigen's makeHouseholder)."""
+    QR (LAPACK dgeqrf uses the same reflector convention as Eigen's makeHouseholder).  decisions: a list that receives
+    the d2 of every gate decision, in order."""
     man, N = filt.man, filt.man.N
     H = np.array(H, dtype=float)
     R = np.array(R, dtype=float)
@@ -263,6 +264,8 @@ def msckf_update_ekf(filt, z, zmean, H, R, gate=True):
     while i < len(idx) // 2:
         r = innov[[idx[2 * i], idx[2 * i + 1]]]
         d2 = r @ info[2 * i:2 * i + 2, 2 * i:2 * i + 2] @ r
+        if gate and decisions is not None:
+            decisions.append(float(d2))
         if gate and not d2 < CHI2_95[2]:
             erase(idx, 2 * i)
             erase(idx, 2 * i + 1)

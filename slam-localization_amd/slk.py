@@ -162,11 +162,12 @@ def _rows(a, B, width):
     return _Arg(a.ctypes.data, a.shape[1], HOST, a)
 
 
-def _zrows(z, B, m):
+def _zrows(z, B, m, name="z"):
     """Measurement rows: the C ABI has no stride for z, slk_update / slk_step always read [B][m] doubles.  A single
-    row is therefore broadcast to every filter here (numpy), device tensors must already hold B * m values."""
+    row is therefore broadcast to every filter here (numpy), tensors must already hold B * m contiguous float64 values."""
     if _is_dev(z):
-        assert z.is_contiguous() and z.numel() == B * m, (tuple(z.shape), B, m)
+        if not z.is_contiguous() or z.numel() != B * m or str(z.dtype) != "torch.float64":
+            raise SlkError(f"{name} must be a contiguous float64 tensor of {B} x {m} values, got {z.dtype} {tuple(z.shape)}")
         return _Arg(z.data_ptr(), m, DEVICE if z.is_cuda else HOST, z)
     z = np.asarray(z, dtype=np.float64)
     assert z.shape[-1] == m and (z.ndim == 1 or z.shape[0] in (1, B)), (z.shape, B, m)
@@ -178,7 +179,9 @@ def _mat(M, B, n):
     """n x n matrix, shared [n, n] or per-filter [B, n, n] (numpy: row/col indexable; torch device tensors
     must already be column-major per filter -- symmetric matrices are either way)."""
     if _is_dev(M):
-        assert M.is_contiguous()
+        if not M.is_contiguous() or str(M.dtype) != "torch.float64" or tuple(M.shape) not in ((n, n), (B, n, n)):
+            raise SlkError(f"matrix must be a contiguous float64 tensor [{n}, {n}] or [{B}, {n}, {n}], "
+                           f"got {M.dtype} {tuple(M.shape)}")
         stride = 0 if M.dim() == 2 else int(M.stride(0))
         return _Arg(M.data_ptr(), stride, DEVICE if M.is_cuda else HOST, M)
     M = np.asarray(M, dtype=np.float64)
@@ -219,7 +222,8 @@ def _steps(a, T, B, width, name, exact=False, per_filter=False):
 
 def _where(*args):
     ws = {a.where for a in args if a.where is not None}
-    assert len(ws) == 1, "all arguments of one call must live on the same side (host or device)"
+    if len(ws) != 1:                                          # (a host address read as a device one is a page fault)
+        raise SlkError("all arguments of one call must live on the same side (host or device)")
     return ws.pop()
 
 
@@ -599,22 +603,23 @@ class Msckf(_FilterBatch):
     def update_ekf(self, z, zmean, H, R, gate=True):
         """EKF update(z, h, H, R) (Msckf.hpp:284-349): zmean [B, m] = h(mu), H [B, m, N] = its Jacobian (numpy, row/col
         indexable), evaluated by the caller at the current mean like the reference's functor h(mu_state, H).
-        Device tensors are taken as they are: z, zmean [B, m], H [B, N, m] (= m x N column-major per filter), R column-major."""
-        if _is_dev(H):
-            m = int(z.shape[-1])
-            ra = _mat(R, self.B, m)
-            assert z.is_contiguous() and zmean.is_contiguous() and H.is_contiguous()
-            assert z.numel() == self.B * m and zmean.numel() == self.B * m and H.numel() == self.B * m * self.N
-            _check(self._lib.slk_update_ekf(self._h, z.data_ptr(), zmean.data_ptr(), H.data_ptr(), m, ra.ptr, ra.stride,
-                                            int(bool(gate)), DEVICE), "slk_update_ekf")
-            return
+        Tensors are taken as they are: z, zmean [B, m], H [B, N, m] (= m x N column-major per filter), R [m, m] or
+        [B, m, m] column-major, all contiguous float64 and all on the same side; torch's stream is synchronised before a
+        device launch."""
+        B, N = self.B, self.N
         m = int(np.shape(z)[-1])
-        z = np.ascontiguousarray(np.broadcast_to(np.asarray(z, dtype=np.float64).reshape(-1, m), (self.B, m)))
-        zm = np.ascontiguousarray(np.broadcast_to(np.asarray(zmean, dtype=np.float64).reshape(-1, m), (self.B, m)))
-        Hc = np.ascontiguousarray(np.transpose(np.asarray(H, dtype=np.float64).reshape(self.B, m, self.N), (0, 2, 1)))
-        ra = _mat(np.asarray(R), self.B, m)
-        _check(self._lib.slk_update_ekf(self._h, z.ctypes.data, zm.ctypes.data, Hc.ctypes.data, m, ra.ptr, ra.stride,
-                                        int(bool(gate)), HOST), "slk_update_ekf")
+        za, zma, ra = _zrows(z, B, m), _zrows(zmean, B, m, "zmean"), _mat(R, B, m)
+        if _is_dev(H):
+            ha = _zrows(H, B, m * N, "H")
+        else:
+            Hc = np.ascontiguousarray(np.transpose(np.asarray(H, dtype=np.float64).reshape(B, m, N), (0, 2, 1)))
+            ha = _Arg(Hc.ctypes.data, m * N, HOST, Hc)
+        where = _where(za, zma, ha, ra)
+        if where == DEVICE:
+            import torch
+            torch.cuda.current_stream(H.device).synchronize()  # (the handle's stream does not wait for torch's)
+        _check(self._lib.slk_update_ekf(self._h, za.ptr, zma.ptr, ha.ptr, m, ra.ptr, ra.stride, int(bool(gate)), where),
+               "slk_update_ekf")
 
     def checkSigmaPoints(self):
         """checkSigmaPoints() (Msckf.hpp:819-839) on the device: returns (max |covSigmaPoints - Pk| [B],

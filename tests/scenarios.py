@@ -156,17 +156,20 @@ def synthetic_usckf(B, nfk=3, nfkl=9, seed=0x5EED1000):
                 R=0.01 * np.eye(nfk))
 
 
-def synthetic_ekf(B, k, m, seed=0xEC0F, outliers=True):
+def synthetic_ekf(B, k, m, seed=0xEC0F, outliers=True, dense=False):
     """Inputs of the Msckf EKF update (Msckf.hpp:284-349) for B filters with k clones: what the reference's functor
     h(mu_state, H) hands back (zmean, H [m x N]) plus z and a non-isotropic R.  The Jacobians have exactly zero
     columns for velocity / angular velocity (as stacked feature residuals do) and are dense elsewhere: the exact
     zeros are handled identically by every Householder sweep (tau = 0), whereas a numerically dependent column would
-    make thinQ -- and with a non-isotropic R the result -- depend on rounding noise."""
+    make thinQ -- and with a non-isotropic R the result -- depend on rounding noise.
+    dense=True keeps those columns too: a dense Jacobian of full column rank (m >= N), whose thinQ spans the range of H
+    whatever the rounding."""
     s = synthetic_msckf(B, k, m=2, seed=seed)
     N = s["N"]
     rng = np.random.default_rng(seed + 1)
     H = rng.normal(0, 1.0, (B, m, N))
-    H[:, :, 6:12] = 0.0
+    if not dense:
+        H[:, :, 6:12] = 0.0
     A = rng.normal(0, 0.05, (B, m, m))
     R = A @ np.transpose(A, (0, 2, 1)) + 0.02 * np.eye(m)
     zmean = rng.normal(0, 1.0, (B, m))
@@ -176,6 +179,37 @@ def synthetic_ekf(B, k, m, seed=0xEC0F, outliers=True):
             for r in rng.choice(m // 2, size=1 + b % 3, replace=False):
                 z[b, 2 * r] += 25.0
     return dict(B=B, k=k, m=m, N=N, Nq=s["Nq"], mean=s["mean"], P=s["P"].reshape(B, N, N), H=H, R=R, z=z, zmean=zmean)
+
+
+EKF_EDGE_CASES = ("first", "last", "adjacent", "all", "rows_N", "rows_N-2")
+
+
+def ekf_outlier_rows(case, m, N):
+    """Rows of an m-row EKF measurement to push out of the gate, and the number of pairs the reference's removeOutliers
+    (Msckf.hpp:756-789) then rejects.  A rejection at list position i erases the pair's first row, then -- the second
+    erase shifted by the first -- the first row of the NEXT pair, and re-tests position i:
+      first     row 0 (pair 0): one rejection, rows 1 and 3 form the re-tested pair
+      last      row m - 1: one rejection; the second erase runs past the end and drops the last row
+      adjacent  rows 6 and 9 (pairs 3 and 4): three rejections (the re-tested pairs (7, 9) and (9, 11) hold row 9)
+      all       every row: m / 2 rejections, no row left
+      rows_N    the first L = m - N - 1 rows: after j rejections the list starts 2j - 1, 2j + 1, 2j + 2, ..., so
+                ceil((L + 1) / 2) = (m - N) / 2 rejections leave exactly N rows
+      rows_N-2  the first m - N + 1 rows: N - 2 rows left, fewer than reduceDimension needs"""
+    return {"first": ([0], 1), "last": ([m - 1], 1), "adjacent": ([6, 9], 3), "all": (list(range(m)), m // 2),
+            "rows_N": (list(range(m - N - 1)), (m - N) // 2),
+            "rows_N-2": (list(range(m - N + 1)), (m - N + 2) // 2)}[case]
+
+
+def ekf_gate_edge(B, k, m, case, seed=0xED6E):
+    """synthetic_ekf inputs (dense H) whose gate decisions do not depend on rounding: the innovation is 0.01-scale noise
+    (d2 far below 5.99) except on the rows of ekf_outlier_rows(case), which are 25 off (d2 far above).  Adds n_out,
+    the number of pairs the gate rejects."""
+    e = synthetic_ekf(B, k, m, seed=seed, outliers=False, dense=True)
+    rows, n_out = ekf_outlier_rows(case, m, e["N"])
+    z = e["zmean"] + np.random.default_rng(seed + 2).normal(0, 0.01, (B, m))
+    z[:, rows] += 25.0
+    e.update(z=z, n_out=n_out)
+    return e
 
 
 def synthetic_pose_ops(B=24, seed=0xD0E5):
