@@ -7,6 +7,7 @@
  *                                                              -> slk_update / slk_update_from_sigma /
  *                                                                 slk_update_innovation + slk_update_selected
  *   EKF update(z, h, H, R) :284-290, update(z, h, H, R, mt) :297-349 -> slk_update_ekf
+ *   ... with h = slk::FeatureProjectionModel                          -> slk_update_ekf_model (slk_ekf_linearize for a custom mt)
  *   muSingleState / setPkSingleState / getPkSingleState / muState (const and non-const) / getPk / setPk :351-395
  *   checkSigmaPoints :819-839 -> slk_check_sigma_points;  accept_mahalanobis_distance :844-905
  *
@@ -184,6 +185,12 @@ namespace localization
             return finish_update();
         }
         struct NoTest { bool operator()(const ScalarType &, int) const { return true; } };
+        /** h(mu) and H already evaluated (slk_ekf_linearize): the functor the caller-gated EKF update calls */
+        template <class Z> struct Linearised
+        {
+            const Z &mean_z;
+            template <class Jac> Z operator()(const _MultiState &, Jac &) const { return mean_z; }
+        };
 
         template <class T> static int kind_of(const T &) { return 2; }
         static int kind_of(const bool &g) { return g ? 1 : 0; }
@@ -338,6 +345,37 @@ namespace localization
             device_changed();
             last_outliers = nout;
             return nout;
+        }
+
+        /**@brief EKF update from a REGISTERED measurement model: slk::FeatureProjectionModel in place of the functor
+         * h(mu_state, H).  The library linearises the model at the resident mean on the device (slk_update_ekf_model):
+         * neither the mean nor the Jacobian crosses to the host, and H is left as it is.  Returns the outlier count. */
+        template <typename _Measurement, class Jac, class Cov>
+        typename std::enable_if<slk::is_matrix_like<Jac>::value && slk::is_matrix_like<Cov>::value, unsigned int>::type
+        update(const _Measurement &z, const slk::FeatureProjectionModel &hmodel, Jac &H, Cov &R)
+        {
+            return update(z, hmodel, H, R, true);
+        }
+        /**@brief ... with a significance test.  A custom test needs h(mu) and H on the host: slk_ekf_linearize fills H
+         * (m x N, sized by the caller) and the caller-gated code of the functor form above runs on them. */
+        template <typename _Measurement, class Jac, class Cov, typename _SignificanceTest>
+        unsigned int update(const _Measurement &z, const slk::FeatureProjectionModel &hmodel, Jac &H, Cov &R, _SignificanceTest mt)
+        {
+            sync_device();
+            const int m = (int)z.size(), N = h.N(), kind = kind_of(mt);
+            if (kind < 2) {
+                slk::check(slk_update_ekf_model(h.get(), model_id(hmodel), model_params(hmodel), 0, z.data(), m, R.data(), 0, kind,
+                                                SLK_HOST), "slk_update_ekf_model");
+                return finish_update();
+            }
+            if ((int)H.rows() != m || (int)H.cols() != N) throw std::invalid_argument("Msckf::update: H must be m x N");
+            _Measurement mean_z(z);
+            std::vector<double> zm(m);
+            slk::check(slk_ekf_linearize(h.get(), model_id(hmodel), model_params(hmodel), 0, m, zm.data(), H.data(), SLK_HOST),
+                       "slk_ekf_linearize");
+            for (int r = 0; r < m; ++r) mean_z[r] = zm[r];
+            Linearised<_Measurement> lin = {mean_z};
+            return update(z, lin, H, R, mt);
         }
 
         void muSingleState(const _SingleState &state)            // Msckf.hpp:351-354

@@ -216,6 +216,48 @@ int slk_update_selected(slk_filter *f, int model, const double *params, int p_st
 int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const double *H, int m,
                    const double *R, int r_stride, int gate, int where);
 
+/* ---- EKF update from a REGISTERED measurement model (Tier A for the EKF update; the reference has no such call: its
+ *      functor h(mu_state, H) is host code).  The library linearises the model at the resident mean on the device, so
+ *      nothing of the state or of the Jacobian crosses to the host.  Msckf only, model = SLK_MM_FEATURE_PROJ only
+ *      (SLK_MM_POSE_POSITION has m = 3 < N rows, SLK_MM_VO_RELATIVE is a Usckf model, SLK_MODEL_EXTERNAL is slk_update_ekf
+ *      itself: all SLK_E_INVALID, the filter untouched); params, p_stride as in slk_update; the row rules of
+ *      slk_update_ekf (N <= m <= 512, m even).
+ *      For feature j with landmark Lw seen from pose c (position p, orientation q, tangent offset tp = 0 for the state,
+ *      12 + 6 (c - 1) for clone c - 1), l = R(q)^T (Lw - p):
+ *        zmean[2j .. 2j+1] = (l.x / l.z, l.y / l.z)
+ *        H[2j .. 2j+1, tp .. tp+2] = -J R(q)^T,  H[2j .. 2j+1, tp+3 .. tp+5] = J [l]x,  every other entry an exact +0.0,
+ *        J = [[1/l.z, 0, -l.x/l.z^2], [0, 1/l.z, -l.y/l.z^2]] -- the derivative under the filter's own boxplus
+ *        (p + dp, q * exp(dtheta), State.hpp:186-200, :286-296).  Only the mean is read (a lower-only P needs no pass).
+ *      Pose indices: host-resident parameters with an index outside 0 .. k (or NaN) are SLK_E_INVALID before any launch;
+ *      device-resident ones give that filter SLK_ST_BAD_INDEX, its update is skipped (mean, P, outlier count untouched),
+ *      the other filters are unaffected; slk_ekf_linearize fills the zmean / H of such a filter with NaN.
+ *      slk_ekf_linearize: zmean [B][m] and H [B][m*N] (m x N column-major per filter, the layout slk_update_ekf takes)
+ *        into caller memory; mean and P are not modified.
+ *      slk_update_ekf_model: mean, P, status bits and outlier counts are bit-identical to slk_ekf_linearize(SLK_DEVICE)
+ *        into caller buffers followed by slk_update_ekf(SLK_DEVICE) on them (two launches: the linearisation into a
+ *        workspace of the handle, then slk_update_ekf's kernel of that shape, unchanged) -- except for a filter with a
+ *        bad device-resident pose index: here it is skipped and stays untouched, whereas slk_update_ekf fed the NaN
+ *        zmean / H of slk_ekf_linearize would run its update on them.
+ *        gate (here, in slk_step_ekf and as slk_traj::gate in slk_step_n_ekf) is read as zero / non-zero: 0 = accept
+ *        all 2-row blocks, anything else = accept_mahalanobis_distance as in slk_update_ekf (there is no caller-gated
+ *        value 2 as in the UKF step).
+ *      slk_step_ekf: slk_predict followed by slk_update_ekf_model, bit-identical; the state does not leave the device.
+ *      slk_step_n_ekf: slk_step_n_slide (slide may be NULL) with slk_step_ekf as the step: everything slk_step_n and
+ *        slk_step_n_slide promise -- every check and every reservation (this workspace and slk_update_ekf's included)
+ *        before the first launch, one upload per input on the host route, no host synchronisation between steps, the
+ *        records of a step taken after its slide -- with T x (slk_step_ekf, then slk_msckf_drop_clone + slk_msckf_clone_pose
+ *        where slide[t] >= 0) as the bit-identical yardstick.  slk_traj is read as by slk_step_n.
+ *      Workspace: B * (m * N + m) doubles for zmean and H plus one int per filter (the skip flags of bad pose indices),
+ *      rounded up to 8 doubles, kept by the handle between calls like every other workspace, next to slk_update_ekf's
+ *      own; a failed reservation returns before any launch. ---- */
+int slk_ekf_linearize(slk_filter *f, int model, const double *params, int p_stride, int m,
+                      double *zmean, double *H, int where);
+int slk_update_ekf_model(slk_filter *f, int model, const double *params, int p_stride,
+                         const double *z, int m, const double *R, int r_stride, int gate, int where);
+int slk_step_ekf(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,
+                 int mmodel, const double *params, int p_stride, const double *z, int m,
+                 const double *R, int r_stride, int gate, int where);
+
 /* ---- fused predict + update, one kernel launch, state stays on chip between the two
  *      (the benchmark's "filter step") ---- */
 int slk_step(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,
@@ -272,6 +314,8 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where);
  *      handle, is SLK_E_INVALID and leaves the filter untouched.  The schedule is a separate argument: slk_traj and
  *      its size are those of slk_step_n. ---- */
 int slk_step_n_slide(slk_filter *f, const slk_traj *t, const int *slide, int where);
+/* slk_step_n_slide with slk_step_ekf as the step (see slk_update_ekf_model above; slide may be NULL) */
+int slk_step_n_ekf(slk_filter *f, const slk_traj *t, const int *slide, int where);
 
 /* ---- Tier B (opaque host functors, the reference's boost::bind form:
  *      UsckfUnitTest.cpp:246,284; MsckfUnitTest.cpp:200-205).  The library draws the sigma

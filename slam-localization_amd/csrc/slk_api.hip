@@ -18,6 +18,7 @@
 #include "slk_usckf.hpp"
 #include "slk_ekf.hpp"
 #include "slk_ekf_tiles.hpp"
+#include "slk_ekf_model.hpp"
 #include "slk_pose.hpp"
 #include "slk_consistency.hpp"
 #include "slk_trajectory.hpp"
@@ -68,6 +69,7 @@ struct slk_filter {
     Stage st_u, st_Q, st_mp, st_z, st_R, st_X, st_Z, st_tmpP, st_tmpM;
     Stage ws_L, ws_DR;            // large-state workspaces (N > 80), allocated on first use
     Stage ws_ekf;                 // EKF update workspace, allocated on first use
+    Stage ws_lin;                 // EKF update from a registered model: zmean, H of the linearisation and its skip flags
     Stage ws_cons;                // slk_nees / slk_sample_states workspace (consistency_ws), allocated on first use
     Stage st_truth, st_rec;       // slk_step_n (host route): the truths of all steps, the device copy of the records
     // Msckf rotation-item descriptors, one table per window length k the handle has run (a sliding window alternates
@@ -171,7 +173,7 @@ void slk_destroy(slk_filter *f)
     (void)hipSetDevice(f->cfg.device);
     (void)hipStreamSynchronize(f->stream);
     Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_X, &f->st_Z, &f->st_tmpP, &f->st_tmpM,
-                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_cons, &f->st_truth, &f->st_rec};
+                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_cons, &f->st_truth, &f->st_rec};
     for (Stage *s : st) if (s->p) (void)hipFree(s->p);
     for (auto &kv : f->rtabs) if (kv.second.dev) (void)hipFree(kv.second.dev);
     if (f->d_mean) (void)hipFree(f->d_mean);
@@ -603,6 +605,22 @@ static int fill_predict(slk_filter *f, KArgs &a, int model, const double *u, int
     return stage_in(f, f->st_Q, Q, q_stride ? (size_t)f->B * q_stride : (size_t)144, where, &a.Q);
 }
 
+// pose indices are caller data: reject anything outside 0..k (Msckf) / 0..2 (Usckf) before it reaches a kernel
+// (host-resident parameters; device-resident ones are checked by the kernel itself: SLK_ST_BAD_INDEX)
+static int check_pose_indices(slk_filter *f, int model, const double *params, int p_stride, int m)
+{
+    const double maxc = f->lay.kind == SLK_MSCKF ? (double)f->lay.k : 2.0;
+    const int rows = p_stride ? f->B : 1;
+    for (int b = 0; b < rows; ++b) {
+        const double *row = params + (size_t)b * p_stride;
+        if (model == SLK_MM_FEATURE_PROJ) {
+            for (int q = 0; q < m / 2; ++q)
+                if (!(row[4 * q + 3] >= 0.0 && row[4 * q + 3] <= maxc)) { g_err = "pose index of a feature out of range"; return SLK_E_INVALID; }
+        } else if (!(row[0] >= 0.0 && row[0] <= maxc)) { g_err = "pose index out of range"; return SLK_E_INVALID; }
+    }
+    return SLK_OK;
+}
+
 // every check of an update's arguments (host-resident parameters: their pose indices too)
 static int check_update(slk_filter *f, int model, const double *params, int p_stride, const double *z, int m,
                         const double *R, int r_stride, int where)
@@ -623,19 +641,7 @@ static int check_update(slk_filter *f, int model, const double *params, int p_st
     }
     int np = mm_params(model, m);
     if (np && (!params || (p_stride != 0 && p_stride < np))) return SLK_E_INVALID;
-    if (np && where == SLK_HOST) {
-        // pose indices are caller data: reject anything outside 0..k (Msckf) / 0..2 (Usckf) before it reaches a kernel
-        // (device-resident parameters are checked by the kernel itself: SLK_ST_BAD_INDEX)
-        const double maxc = f->lay.kind == SLK_MSCKF ? (double)f->lay.k : 2.0;
-        const int rows = p_stride ? f->B : 1;
-        for (int b = 0; b < rows; ++b) {
-            const double *row = params + (size_t)b * p_stride;
-            if (model == SLK_MM_FEATURE_PROJ) {
-                for (int q = 0; q < m / 2; ++q)
-                    if (!(row[4 * q + 3] >= 0.0 && row[4 * q + 3] <= maxc)) { g_err = "pose index of a feature out of range"; return SLK_E_INVALID; }
-            } else if (!(row[0] >= 0.0 && row[0] <= maxc)) { g_err = "pose index out of range"; return SLK_E_INVALID; }
-        }
-    }
+    if (np && where == SLK_HOST) return check_pose_indices(f, model, params, p_stride, m);
     return SLK_OK;
 }
 
@@ -919,6 +925,180 @@ int slk_update(slk_filter *f, int model, const double *params, int p_stride, con
     return launch(f, a);
 }
 
+} // extern "C"
+
+// The workspace of the EKF kernels at m rows and, for the tile kernel, its LDS size: everything that can fail ahead of
+// launch_ekf.
+static int reserve_ekf(slk_filter *f, int m)
+{
+    const int N = f->lay.N;
+    int rc = stage_reserve(f, f->ws_ekf, (size_t)f->B * ekf_ws_doubles(N, m));
+    if (rc) return rc;
+#ifndef SLK_DEV_N60
+    if (m <= 128 && N <= 64)
+        return ensure_dynamic_lds(reinterpret_cast<const void *>(msckf_ekf_tile_kernel<1024>), f->cfg.device,
+                                  ekf_tile_lds_doubles(N, m) * sizeof(double));
+#endif
+    return SLK_OK;
+}
+
+// The EKF update kernel of this shape on filled arguments (reserve_ekf made).
+static int launch_ekf(slk_filter *f, EkfArgs a)
+{
+    a.ws = f->ws_ekf.p;
+#ifdef SLK_STAMPS
+    a.dbg = g_dbg;
+#endif
+#ifdef SLK_DEV_N60
+    g_err = "development build: no EKF kernels"; return SLK_E_UNSUPPORTED;
+#else
+    if (a.m <= 128 && a.N <= 64) {                                // everything resident in LDS as 16 x 16 tiles
+        const size_t lds = ekf_tile_lds_doubles(a.N, a.m) * sizeof(double);
+        hipLaunchKernelGGL(msckf_ekf_tile_kernel<1024>, dim3(f->B), dim3(1024), lds, f->stream, a);
+    } else {
+        hipLaunchKernelGGL(msckf_ekf_kernel<256>, dim3(f->B), dim3(256), 0, f->stream, a);
+    }
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+#endif
+}
+
+static void ekf_base_args(slk_filter *f, EkfArgs &a, int m, int gate, int r_stride)
+{
+    memset(&a, 0, sizeof(a));
+    a.B = f->B; a.N = f->lay.N; a.Nq = f->lay.Nq; a.k = f->lay.k; a.m = m; a.gate = gate;
+    a.mean = f->d_mean; a.P = f->d_P; a.status = f->d_status; a.outliers = f->d_outliers;
+    a.r_stride = r_stride;
+}
+
+// ---------------------------------------------------------------------------- EKF update from a registered model
+// zmean / H of the handle's own linearisation: [B][m], [B][m*N], then one skip flag (int) per filter
+static size_t lin_ws_doubles(const slk_filter *f, int m)
+{
+    const size_t B = (size_t)f->B, n = B * ((size_t)m * f->lay.N + m) + (B * sizeof(int) + sizeof(double) - 1) / sizeof(double);
+    return (n + 7) / 8 * 8;
+}
+static double *lin_zmean(slk_filter *f) { return f->ws_lin.p; }
+static double *lin_H(slk_filter *f, int m) { return f->ws_lin.p + (size_t)f->B * m; }
+static int *lin_skip(slk_filter *f, int m) { return reinterpret_cast<int *>(f->ws_lin.p + (size_t)f->B * ((size_t)m * f->lay.N + m)); }
+
+// Msckf, SLK_MM_FEATURE_PROJ, the row rules of slk_update_ekf; host-resident parameters: their pose indices too
+static int check_ekf_model(slk_filter *f, int model, const double *params, int p_stride, int m, int where)
+{
+    if (!f || f->lay.kind != SLK_MSCKF || model != SLK_MM_FEATURE_PROJ || !params) return SLK_E_INVALID;
+    if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
+    if (m < f->lay.N || m > 512 || (m & 1)) return SLK_E_INVALID;
+    if (p_stride != 0 && p_stride < mm_params(model, m)) return SLK_E_INVALID;
+    if (where == SLK_HOST) return check_pose_indices(f, model, params, p_stride, m);
+    return SLK_OK;
+}
+
+static int launch_linearize(slk_filter *f, const double *dmp, int p_stride, int m, double *zmean, double *H, int *skip)
+{
+    LinArgs a;
+    a.B = f->B; a.N = f->lay.N; a.Nq = f->lay.Nq; a.k = f->lay.k; a.m = m;
+    a.mean = f->d_mean; a.mp = dmp; a.mp_stride = p_stride; a.zmean = zmean; a.H = H; a.status = f->d_status; a.skip = skip;
+    hipLaunchKernelGGL(msckf_ekf_linearize_kernel, dim3(f->B), dim3(LIN_THREADS), 0, f->stream, a);
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+}
+
+// every reservation of one model-driven EKF update at m rows
+static int reserve_ekf_model(slk_filter *f, int m)
+{
+    int rc = stage_reserve(f, f->ws_lin, lin_ws_doubles(f, m));
+    if (rc) return rc;
+    return reserve_ekf(f, m);
+}
+
+// linearise at the resident mean into the handle's workspace, then the EKF kernel on it: device pointers, checks and
+// reservations (reserve_ekf_model) made by the caller.  Exactly what slk_ekf_linearize + slk_update_ekf enqueue on
+// device-resident buffers, plus the skip flags.
+static int launch_ekf_model(slk_filter *f, const double *dmp, int p_stride, const double *dz, int m, const double *dR,
+                            int r_stride, int gate)
+{
+    int rc = mirror_upper(f);
+    if (rc) return rc;
+    rc = launch_linearize(f, dmp, p_stride, m, lin_zmean(f), lin_H(f, m), lin_skip(f, m));
+    if (rc) return rc;
+    EkfArgs a;
+    ekf_base_args(f, a, m, gate, r_stride);
+    a.z = dz; a.zmean = lin_zmean(f); a.H = lin_H(f, m); a.R = dR; a.skip = lin_skip(f, m);
+    return launch_ekf(f, a);
+}
+
+extern "C" {
+
+int slk_ekf_linearize(slk_filter *f, int model, const double *params, int p_stride, int m, double *zmean, double *H, int where)
+{
+    int rc = check_ekf_model(f, model, params, p_stride, m, where);
+    if (rc) return rc;
+    if (!zmean || !H) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t B = (size_t)f->B, N = (size_t)f->lay.N;
+    const double *dmp;
+    rc = stage_in(f, f->st_mp, params, p_stride ? B * p_stride : (size_t)mm_params(model, m), where, &dmp);
+    if (rc) return rc;
+    if (where == SLK_DEVICE) return launch_linearize(f, dmp, p_stride, m, zmean, H, nullptr);
+    rc = stage_reserve(f, f->ws_lin, lin_ws_doubles(f, m));
+    if (rc) return rc;
+    rc = launch_linearize(f, dmp, p_stride, m, lin_zmean(f), lin_H(f, m), nullptr);
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(zmean, lin_zmean(f), B * m * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHECK(hipMemcpyAsync(H, lin_H(f, m), B * m * N * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHECK(hipStreamSynchronize(f->stream));
+    return SLK_OK;
+}
+
+int slk_update_ekf_model(slk_filter *f, int model, const double *params, int p_stride, const double *z, int m,
+                         const double *R, int r_stride, int gate, int where)
+{
+    int rc = check_ekf_model(f, model, params, p_stride, m, where);
+    if (rc) return rc;
+    if (!z || !R || (r_stride != 0 && r_stride < m * m)) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t B = (size_t)f->B;
+    const double *dmp, *dz, *dR;
+    rc = reserve_ekf_model(f, m);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_mp, params, p_stride ? B * p_stride : (size_t)mm_params(model, m), where, &dmp);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_z, z, B * m, where, &dz);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_R, R, r_stride ? B * r_stride : (size_t)m * m, where, &dR);
+    if (rc) return rc;
+    return launch_ekf_model(f, dmp, p_stride, dz, m, dR, r_stride, gate);
+}
+
+int slk_step_ekf(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,
+                 int mmodel, const double *params, int p_stride, const double *z, int m,
+                 const double *R, int r_stride, int gate, int where)
+{
+    int rc = check_ekf_model(f, mmodel, params, p_stride, m, where);
+    if (rc) return rc;
+    if (!z || !R || (r_stride != 0 && r_stride < m * m)) return SLK_E_INVALID;
+    rc = check_predict(pmodel, u, u_stride, Q, q_stride);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t B = (size_t)f->B;
+    const double *dmp, *dz, *dR;
+    rc = reserve_ekf_model(f, m);
+    if (rc) return rc;
+    KArgs a;
+    base_args(f, a);
+    rc = fill_predict(f, a, pmodel, u, u_stride, Q, q_stride, where);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_mp, params, p_stride ? B * p_stride : (size_t)mm_params(mmodel, m), where, &dmp);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_z, z, B * m, where, &dz);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_R, R, r_stride ? B * r_stride : (size_t)m * m, where, &dR);
+    if (rc) return rc;
+    rc = launch(f, a);                                            // the predict-only call of slk_predict
+    if (rc) return rc;
+    return launch_ekf_model(f, dmp, p_stride, dz, m, dR, r_stride, gate);
+}
+
 int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const double *H, int m,
                    const double *R, int r_stride, int gate, int where)
 {
@@ -929,10 +1109,7 @@ int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const do
     HIPCHECK(hipSetDevice(f->cfg.device));
     { int rcm = mirror_upper(f); if (rcm) return rcm; }
     EkfArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = f->B; a.N = N; a.Nq = f->lay.Nq; a.k = f->lay.k; a.m = m; a.gate = gate;
-    a.mean = f->d_mean; a.P = f->d_P; a.status = f->d_status; a.outliers = f->d_outliers;
-    a.r_stride = r_stride;
+    ekf_base_args(f, a, m, gate, r_stride);
     size_t B = (size_t)f->B;
     int rc = stage_in(f, f->st_z, z, B * m, where, &a.z);
     if (rc) return rc;
@@ -942,27 +1119,9 @@ int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const do
     if (rc) return rc;
     rc = stage_in(f, f->st_R, R, r_stride ? B * r_stride : (size_t)m * m, where, &a.R);
     if (rc) return rc;
-    rc = stage_reserve(f, f->ws_ekf, B * ekf_ws_doubles(N, m));
+    rc = reserve_ekf(f, m);
     if (rc) return rc;
-    a.ws = f->ws_ekf.p;
-#ifdef SLK_STAMPS
-    a.dbg = g_dbg;
-#endif
-#ifdef SLK_DEV_N60
-    g_err = "development build: no EKF kernels"; return SLK_E_UNSUPPORTED;
-#else
-    const size_t lds = ekf_tile_lds_doubles(N, m) * sizeof(double);
-    if (m <= 128 && N <= 64) {                                    // everything resident in LDS as 16 x 16 tiles
-        auto kern = msckf_ekf_tile_kernel<1024>;
-        rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), f->cfg.device, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(f->B), dim3(1024), lds, f->stream, a);
-    } else {
-        hipLaunchKernelGGL(msckf_ekf_kernel<256>, dim3(f->B), dim3(256), 0, f->stream, a);
-    }
-    HIPCHECK(hipGetLastError());
-    return SLK_OK;
-#endif
+    return launch_ekf(f, a);
 }
 
 int slk_step(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,
@@ -1453,9 +1612,10 @@ static int prepare_step(slk_filter *f, const KArgs &a)
 
 extern "C" {
 
-// slk_step_n and slk_step_n_slide: slide == NULL is slk_step_n; slide[t] >= 0 slides the window after step t, before
-// that step's records.
-static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
+// slk_step_n, slk_step_n_slide and slk_step_n_ekf: slide == NULL is slk_step_n; slide[t] >= 0 slides the window after
+// step t, before that step's records.  ekf: every step is slk_step_ekf (predict, linearisation, EKF kernel) instead of
+// slk_step; the checks of the measurement side and the reservations are those of slk_step_ekf, everything else is shared.
+static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where, bool ekf = false)
 {
     if (!f || !t || t->T < 1 || t->mmodel == SLK_MODEL_EXTERNAL) return SLK_E_INVALID;
     if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
@@ -1472,7 +1632,12 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
     }
     int rc = check_predict(t->pmodel, t->u, t->u_stride, t->Q, t->q_stride);
     if (rc) return rc;
-    rc = check_update(f, t->mmodel, t->params, t->p_stride, t->z, m, t->R, t->r_stride, SLK_DEVICE);
+    if (ekf) {
+        rc = check_ekf_model(f, t->mmodel, t->params, t->p_stride, m, SLK_DEVICE);
+        if (!rc && (!t->z || !t->R || (t->r_stride != 0 && t->r_stride < m * m))) rc = SLK_E_INVALID;
+    } else {
+        rc = check_update(f, t->mmodel, t->params, t->p_stride, t->z, m, t->R, t->r_stride, SLK_DEVICE);
+    }
     if (rc) return rc;
     const int np = mm_params(t->mmodel, m);
     // one step's block of each input (what slk_step reads), and what all T steps read
@@ -1496,8 +1661,9 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
     if (np && where == SLK_HOST) {                              // the pose indices of every step's parameters
         const int nblk = t->p_tstride ? T : 1;
         for (int s = 0; s < nblk; ++s) {
-            rc = check_update(f, t->mmodel, t->params + (size_t)s * t->p_tstride, t->p_stride, t->z, m, t->R, t->r_stride,
-                              SLK_HOST);
+            const double *ps = t->params + (size_t)s * t->p_tstride;
+            rc = ekf ? check_pose_indices(f, t->mmodel, ps, t->p_stride, m)
+                     : check_update(f, t->mmodel, ps, t->p_stride, t->z, m, t->R, t->r_stride, SLK_HOST);
             if (rc) return rc;
         }
     }
@@ -1505,7 +1671,7 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
     KArgs a;
     base_args(f, a);
     a.do_predict = 1; a.pm = t->pmodel; a.u_stride = t->u_stride; a.q_stride = t->q_stride;
-    a.do_update = 1; a.mm = t->mmodel; a.m = m; a.gate = t->gate; a.mp_stride = t->p_stride; a.r_stride = t->r_stride;
+    if (!ekf) { a.do_update = 1; a.mm = t->mmodel; a.m = m; a.gate = t->gate; a.mp_stride = t->p_stride; a.r_stride = t->r_stride; }
     // ---- every reservation, before the first launch
     const size_t su = span(t->u_tstride, bu), sq = span(t->q_tstride, bq), sp = np ? span(t->p_tstride, bp) : 0;
     const size_t sz = span(t->z_tstride, bz), sr = span(t->r_tstride, br);
@@ -1517,7 +1683,7 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
         const size_t n[] = {su, sq, sp, sz, sr, sth, nmean + nnees + nout};
         for (int i = 0; i < 7; ++i) if (n[i]) { rc = stage_reserve(f, *st[i], n[i]); if (rc) return rc; }
     }
-    rc = prepare_step(f, a);
+    rc = ekf ? reserve_ekf_model(f, m) : prepare_step(f, a);     // (a predict-only launch reserves nothing)
     if (rc) return rc;
     if (any_slide) { rc = reserve_slide(f); if (rc) return rc; }
     const bool nees_rows = want_nees && t->nees_n <= NEES_ROWS_MAX;     // the one-wave record kernel: no workspace
@@ -1543,18 +1709,20 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
         dnees = want_nees ? f->st_rec.p + nmean : nullptr;
         dout = t->outliers_hist ? reinterpret_cast<unsigned *>(f->st_rec.p + nmean + nnees) : nullptr;
     }
-    a.u = du; a.Q = dq; a.mp = dp; a.z = dz; a.R = dr;
+    a.u = du; a.Q = dq;
+    if (!ekf) { a.mp = dp; a.z = dz; a.R = dr; }
     // slk_step's launch() per step on the inputs of that step (its route, its bookkeeping), then the records
     for (int s = 0; s < T; ++s) {
         KArgs as = a;
         as.mean = f->d_mean; as.P = f->d_P;                    // (a slide swaps the buffer pairs)
         as.u = du + (size_t)s * t->u_tstride;
         as.Q = dq + (size_t)s * t->q_tstride;
-        as.mp = dp ? dp + (size_t)s * t->p_tstride : nullptr;
-        as.z = dz + (size_t)s * t->z_tstride;
-        as.R = dr + (size_t)s * t->r_tstride;
-        rc = launch(f, as);
+        const double *mps = dp ? dp + (size_t)s * t->p_tstride : nullptr;
+        const double *zs = dz + (size_t)s * t->z_tstride, *rs = dr + (size_t)s * t->r_tstride;
+        if (!ekf) { as.mp = mps; as.z = zs; as.R = rs; }
+        rc = launch(f, as);                                    // (ekf: the predict-only launch)
         if (rc) return rc;
+        if (ekf) { rc = launch_ekf_model(f, mps, t->p_stride, zs, m, rs, t->r_stride, t->gate); if (rc) return rc; }
         if (slide && slide[s] >= 0) { rc = launch_slide(f, slide[s]); if (rc) return rc; }
         if (dmean)
             HIPCHECK(hipMemcpyAsync(dmean + (size_t)s * B * Nq, f->d_mean, B * Nq * sizeof(double), hipMemcpyDeviceToDevice,
@@ -1588,6 +1756,8 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where)
 int slk_step_n(slk_filter *f, const slk_traj *t, int where) { return step_n(f, t, nullptr, where); }
 
 int slk_step_n_slide(slk_filter *f, const slk_traj *t, const int *slide, int where) { return step_n(f, t, slide, where); }
+
+int slk_step_n_ekf(slk_filter *f, const slk_traj *t, const int *slide, int where) { return step_n(f, t, slide, where, true); }
 
 struct slk_adaptive {
     int B, device;

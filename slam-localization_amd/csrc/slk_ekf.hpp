@@ -25,6 +25,8 @@ struct EkfArgs {
     const double *z, *zmean, *H, *R;     // [B][m], [B][m], [B][m*N] column-major, [B or 1][m*m]
     int r_stride;
     double *ws;                          // per-filter workspace, ekf_ws_doubles(N, m) each
+    const int *skip;                     // [B] or NULL: nonzero = leave this filter as it is (a bad pose index found by the
+                                         // linearisation, slk_ekf_model.hpp); uniform over the workgroup
     long long *dbg;                      // phase stamps [B][32], diagnostic builds only
 };
 
@@ -71,6 +73,7 @@ __global__ __launch_bounds__(NTHREADS) void msckf_ekf_kernel(EkfArgs a)
     __shared__ double hh[4];              // beta, tau of the current reflector
     const int tid = threadIdx.x, b = blockIdx.x;
     const int N = a.N, Nq = a.Nq, m = a.m;
+    if (a.skip && a.skip[b]) return;
     double *mean = a.mean + (size_t)b * Nq, *P = a.P + (size_t)b * N * N;
     const double *z = a.z + (size_t)b * m, *zm = a.zmean + (size_t)b * m, *H = a.H + (size_t)b * m * N;
     const double *R = a.R + (size_t)b * a.r_stride;

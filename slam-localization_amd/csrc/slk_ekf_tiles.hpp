@@ -225,6 +225,7 @@ __global__ __launch_bounds__(NTHREADS) void msckf_ekf_tile_kernel(EkfArgs a)
     const int tid = threadIdx.x, b = blockIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int N = a.N, Nq = a.Nq, m = a.m;
     const int NTR = (m + 15) >> 4, NTN = (N + 15) >> 4;
+    if (a.skip && a.skip[b]) return;
     double *mean = a.mean + (size_t)b * Nq, *P = a.P + (size_t)b * N * N;
     const double *z = a.z + (size_t)b * m, *zm = a.zmean + (size_t)b * m, *H = a.H + (size_t)b * m * N;
     const double *R = a.R + (size_t)b * a.r_stride;

@@ -34,6 +34,7 @@ EXPORTS = [
     "slk_check_sigma_points", "slk_update_innovation", "slk_update_selected", "slk_transform_compose",
     "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix", "slk_nees",
     "slk_sample_states", "slk_step_n", "slk_step_n_slide", "slk_msckf_slide",
+    "slk_ekf_linearize", "slk_update_ekf_model", "slk_step_ekf", "slk_step_n_ekf",
 ]
 
 
@@ -118,6 +119,10 @@ def load_library(path=None):
     lib.slk_step_n.argtypes = [vp, C.POINTER(Traj), ip]
     lib.slk_step_n_slide.argtypes = [vp, C.POINTER(Traj), vp, ip]
     lib.slk_msckf_slide.argtypes = [vp, ip]
+    lib.slk_ekf_linearize.argtypes = [vp, ip, vp, ip, ip, vp, vp, ip]
+    lib.slk_update_ekf_model.argtypes = [vp, ip, vp, ip, vp, ip, vp, ip, ip, ip]
+    lib.slk_step_ekf.argtypes = [vp, ip, vp, ip, vp, ip, ip, vp, ip, vp, ip, vp, ip, ip, ip]
+    lib.slk_step_n_ekf.argtypes = [vp, C.POINTER(Traj), vp, ip]
     if path is None:
         _lib = lib
     return lib
@@ -294,8 +299,10 @@ class _FilterBatch:
         """(mean, P) device addresses of the resident state, for zero-copy callers.  Both change after clone_pose,
         drop_clone, slide and a Usckf setMeasurement (the state moves to the handle's second buffer pair): ask again
         after each.  The exact-shape Msckf steps and a slide of their result leave the strict upper triangle of P stale;
-        slk_cov_device_ptr, called here, completes it on the handle's stream, so call device_pointers() again after
-        every step or slide before reading the upper triangle through the pointer."""
+        slk_cov_device_ptr, called here, enqueues the pass that completes it on the handle's stream.  A covariance
+        pointer fetched earlier stays valid as an address but not as a complete matrix: after any further step or slide
+        its strict upper triangle is stale again, so re-fetch the pointer (call device_pointers() again) after the last
+        step and before reading the upper triangle through it; the lower triangle and the diagonal are always current."""
         return self._lib.slk_mean_device_ptr(self._h), self._lib.slk_cov_device_ptr(self._h)
 
     def status(self):
@@ -331,6 +338,11 @@ class _FilterBatch:
             return 1 if self.KIND == MSCKF else 0             # Msckf.hpp:199 / Usckf.hpp:249
         return int(gate)
 
+    def _model_params(self, model, params, m, what):
+        if params is None:
+            raise SlkError(f"{what}: the registered model needs its parameters ((m / 2) x landmark xyz, pose index)")
+        return _rows(params, self.B, _np(model, m))
+
     # ---- Tier A: registered models
     def predict(self, model, u, Q):
         """predict(f, Q), f = registered process model `model` with inputs u (Msckf.hpp:89-95, Usckf.hpp:107-111)."""
@@ -358,8 +370,11 @@ class _FilterBatch:
                "slk_step")
 
     def step_n(self, pmodel, u, Q, z, mmodel, params, R, gate=None, truth=None, nees_range=None, record_mean=False,
-               record_outliers=False, slide=None):
+               record_outliers=False, slide=None, update="ukf"):
         """T fused steps in one call (slk_step_n): the same results as T calls of step() with the inputs of each step.
+        update="ekf" (Msckf, slk_step_n_ekf): every step is step_ekf() instead of step() -- predict, then the EKF update
+        from the registered model mmodel linearised on the device (N <= m <= 512 rows); the arguments, the records and
+        slide= are handled exactly as for the default update="ukf".
         u [T, B, nu] or [T, nu], z [T, B, m], params [T, B, np] or [T, np] (or None), truth [T, B, Nq]: a leading T axis
         always (a stride of 0 there, np.broadcast_to / torch expand, shares one block over all steps); Q and R have the
         shapes step() takes and are shared over the steps.  Records: record_mean -> "mean" [T, B, Nq] (the mean after
@@ -369,6 +384,8 @@ class _FilterBatch:
         slide (slk_step_n_slide): an int d slides the window after every step (drop clone d, clone the current pose),
         or a length-T sequence with -1 (no slide after that step) or d; the records of a step are taken after its
         slide.  The results are those of step() followed by drop_clone(d) + clone_pose() where d >= 0."""
+        if update not in ("ukf", "ekf"):
+            raise SlkError(f"step_n: update must be 'ukf' or 'ekf', got {update!r}")
         T = int(z.shape[0])
         m = int(z.shape[-1])
         B = self.B
@@ -423,7 +440,10 @@ class _FilterBatch:
         tr.mean_hist, tr.outliers_hist, tr.nees_hist = ptr.get("mean"), ptr.get("outliers"), ptr.get("nees")
         if ta is not None:
             tr.truth, tr.truth_tstride, tr.nees_t0, tr.nees_n = ta[0], ta[2], t0, n
-        if sched is None:
+        if update == "ekf":
+            _check(self._lib.slk_step_n_ekf(self._h, C.byref(tr), sched.ctypes.data if sched is not None else None, where),
+                   "slk_step_n_ekf")
+        elif sched is None:
             _check(self._lib.slk_step_n(self._h, C.byref(tr), where), "slk_step_n")
         else:
             _check(self._lib.slk_step_n_slide(self._h, C.byref(tr), sched.ctypes.data, where), "slk_step_n_slide")
@@ -620,6 +640,56 @@ class Msckf(_FilterBatch):
             torch.cuda.current_stream(H.device).synchronize()  # (the handle's stream does not wait for torch's)
         _check(self._lib.slk_update_ekf(self._h, za.ptr, zma.ptr, ha.ptr, m, ra.ptr, ra.stride, int(bool(gate)), where),
                "slk_update_ekf")
+
+    def ekf_linearize(self, model, params, m):
+        """zmean [B, m] = h(mu) and H [B, m, N] = dh/d(tangent) at the resident mean of the registered measurement model
+        `model` (MM_FEATURE_PROJ), computed on the device (slk_ekf_linearize); the filter is not modified.  params as
+        update() takes them.  numpy params -> numpy arrays.  A torch device tensor -> device tensors: H is a [B, m, N]
+        view of the column-major storage, so H.transpose(1, 2) is the contiguous [B, N, m] tensor update_ekf() takes."""
+        B, N, m = self.B, self.N, int(m)
+        pa = self._model_params(model, params, m, "ekf_linearize")
+        if pa.where == DEVICE:
+            import torch
+            torch.cuda.current_stream(params.device).synchronize()   # (the handle's stream does not wait for torch's)
+            zm = torch.empty((B, m), dtype=torch.float64, device=params.device)
+            Hs = torch.empty((B, N, m), dtype=torch.float64, device=params.device)
+            _check(self._lib.slk_ekf_linearize(self._h, model, pa.ptr, pa.stride, m, zm.data_ptr(), Hs.data_ptr(), DEVICE),
+                   "slk_ekf_linearize")
+            self.sync()                                        # torch may read the outputs on any stream
+            return zm, Hs.transpose(1, 2)
+        zm, Hs = np.empty((B, m)), np.empty((B, N, m))
+        _check(self._lib.slk_ekf_linearize(self._h, model, pa.ptr, pa.stride, m, zm.ctypes.data, Hs.ctypes.data, HOST),
+               "slk_ekf_linearize")
+        return zm, np.ascontiguousarray(np.transpose(Hs, (0, 2, 1)))
+
+    def update_ekf_model(self, z, model, params, R, gate=True):
+        """EKF update(z, h, H, R) (Msckf.hpp:284-349) with h and H from the registered model `model` linearised at the
+        resident mean on the device (slk_update_ekf_model): bit-identical to ekf_linearize() + update_ekf() on device
+        tensors, with nothing leaving the device.  z, params, R as update() takes them; N <= m <= 512 rows.  Device
+        tensors are read asynchronously on the handle's stream: keep them alive until sync()."""
+        m = int(np.shape(z)[-1])
+        pa = self._model_params(model, params, m, "update_ekf_model")
+        za, ra = _zrows(z, self.B, m), _mat(R, self.B, m)
+        where = _where(pa, za, ra)
+        if where == DEVICE:
+            import torch
+            torch.cuda.current_stream(z.device).synchronize()  # (the handle's stream does not wait for torch's)
+        _check(self._lib.slk_update_ekf_model(self._h, model, pa.ptr, pa.stride, za.ptr, m, ra.ptr, ra.stride,
+                                              int(bool(gate)), where), "slk_update_ekf_model")
+
+    def step_ekf(self, pmodel, u, Q, z, mmodel, params, R, gate=True):
+        """predict() followed by update_ekf_model(), bit for bit, in one call (slk_step_ekf)."""
+        m = int(np.shape(z)[-1])
+        ua = _rows(u, self.B, 7 if pmodel == PM_CONST_VELOCITY else 13)
+        qa = _mat(Q, self.B, 12)
+        pa = self._model_params(mmodel, params, m, "step_ekf")
+        za, ra = _zrows(z, self.B, m), _mat(R, self.B, m)
+        where = _where(ua, qa, pa, za, ra)
+        if where == DEVICE:
+            import torch
+            torch.cuda.current_stream(z.device).synchronize()  # (the handle's stream does not wait for torch's)
+        _check(self._lib.slk_step_ekf(self._h, pmodel, ua.ptr, ua.stride, qa.ptr, qa.stride, mmodel, pa.ptr, pa.stride,
+                                      za.ptr, m, ra.ptr, ra.stride, int(bool(gate)), where), "slk_step_ekf")
 
     def checkSigmaPoints(self):
         """checkSigmaPoints() (Msckf.hpp:819-839) on the device: returns (max |covSigmaPoints - Pk| [B],
