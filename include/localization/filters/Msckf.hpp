@@ -184,6 +184,15 @@ namespace localization
                        "slk_update_selected");
             return finish_update();
         }
+        template <typename _Measurement, class Cov>
+        double run_nis(const _Measurement &z, int model, const double *params, const std::vector<double> *Z, const Cov &R,
+                       double *logdet)
+        {
+            double r = 0;
+            slk::check(slk_nis(h.get(), model, params, 0, Z ? Z->data() : 0, z.data(), (int)z.size(), R.data(), 0, &r, logdet,
+                               SLK_HOST), "slk_nis");
+            return r;
+        }
         struct NoTest { bool operator()(const ScalarType &, int) const { return true; } };
         /** h(mu) and H already evaluated (slk_ekf_linearize): the functor the caller-gated EKF update calls */
         template <class Z> struct Linearised
@@ -458,6 +467,29 @@ namespace localization
         {
             sync_device();
             slk::check(slk_nees(h.get(), truth, t0, n, nees_out, err, where), "slk_nees");
+        }
+        /**@brief Normalised innovation squared nu^T S^-1 nu of the update that update(z, h, R) would make (all rows, before
+         * any significance test), on the device (slk_nis); logdet, when given, receives log det S, so that the Gaussian
+         * log-likelihood of z is -0.5 (nis + logdet + m log(2 pi)).  NaN if S is not positive definite.  h = registered
+         * model or any callable _MultiState -> vector.  The filter is not modified. */
+        template <typename _Measurement, class Cov>
+        double nis(const _Measurement &z, const slk::FeatureProjectionModel &hmodel, const Cov &R, double *logdet = 0)
+        {
+            sync_device();
+            return run_nis(z, model_id(hmodel), model_params(hmodel), 0, slk::noise_matrix(R, 0), logdet);
+        }
+        template <typename _Measurement, class Cov>
+        double nis(const _Measurement &z, const slk::PosePositionModel &hmodel, const Cov &R, double *logdet = 0)
+        {
+            sync_device();
+            return run_nis(z, model_id(hmodel), model_params(hmodel), 0, slk::noise_matrix(R, 0), logdet);
+        }
+        template <typename _Measurement, typename _MeasurementModel, class Cov>
+        double nis(const _Measurement &z, _MeasurementModel hfun, const Cov &R, double *logdet = 0)
+        {
+            sync_device();
+            const std::vector<double> Z = map_sigma_points<_Measurement>(hfun, (int)z.size());
+            return run_nis(z, SLK_MODEL_EXTERNAL, 0, &Z, slk::noise_matrix(R, 0), logdet);
         }
         /**@brief S draws mu_state [+] L n_s from the filter's own Gaussian (L = chol(Pk), lower, the factor the sigma points
          * come from): noise is N x S, one standard-normal column per draw.  All NaN if Pk is not positive definite. */

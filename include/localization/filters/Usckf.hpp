@@ -295,6 +295,29 @@ namespace localization
         {
             slk::check(slk_nees(h.get(), truth, t0, n, nees_out, err, where), "slk_nees");
         }
+        /**@brief Normalised innovation squared nu^T S^-1 nu of the update that update(z, h, R) would make (all rows, before
+         * any significance test), on the device (slk_nis); logdet, when given, receives log det S, so that the Gaussian
+         * log-likelihood of z is -0.5 (nis + logdet + m log(2 pi)).  NaN if S is not positive definite.  h = the
+         * registered relative-transform model or any callable _AugmentedState -> vector.  The filter is not modified. */
+        template <typename _Measurement, class Cov>
+        double nis(const _Measurement &z, const slk::VoRelativeModel &, const Cov &R, double *logdet = 0)
+        {
+            return run_nis(z, SLK_MM_VO_RELATIVE, 0, slk::noise_matrix(R, 0), logdet);
+        }
+        template <typename _Measurement, typename _MeasurementModel, class Cov>
+        double nis(const _Measurement &z, _MeasurementModel hfun, const Cov &R, double *logdet = 0)
+        {
+            const int N = h.N(), Nq = h.Nq(), S = 2 * N + 1, m = (int)z.size();
+            std::vector<double> X((std::size_t)S * Nq), Z((std::size_t)S * m);
+            slk::check(slk_update_sigma_points(h.get(), X.data(), SLK_HOST), "slk_update_sigma_points");
+            _AugmentedState x;
+            for (int i = 0; i < S; ++i) {                        // std::transform(X, Z, h), Usckf.hpp:277-278
+                slk_load(x, &X[(std::size_t)i * Nq], nfk, nfkl);
+                const _Measurement zi = hfun(x);
+                for (int r = 0; r < m; ++r) Z[(std::size_t)i * m + r] = zi[r];
+            }
+            return run_nis(z, SLK_MODEL_EXTERNAL, &Z, slk::noise_matrix(R, 0), logdet);
+        }
         /**@brief S draws mu_state [+] L n_s from the filter's own Gaussian (L = chol(Pk), lower, the factor the sigma points
          * come from): noise is N x S, one standard-normal column per draw.  All NaN if Pk is not positive definite. */
         std::vector<_AugmentedState> sampleStates(const slk::Matrix &noise)
@@ -325,6 +348,14 @@ namespace localization
         }
 
     private:
+        template <typename _Measurement, class Cov>
+        double run_nis(const _Measurement &z, int model, const std::vector<double> *Z, const Cov &R, double *logdet)
+        {
+            double r = 0;
+            slk::check(slk_nis(h.get(), model, 0, 0, Z ? Z->data() : 0, z.data(), (int)z.size(), R.data(), 0, &r, logdet, SLK_HOST),
+                       "slk_nis");
+            return r;
+        }
         /** library gate: chi-square dof (0 = accept any) */
         template <typename _Measurement, class Cov>
         void run_update(const _Measurement &z, int model, const double *params, const std::vector<double> *Z, const Cov &R, int gate_dof)

@@ -316,6 +316,33 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where);
 int slk_step_n_slide(slk_filter *f, const slk_traj *t, const int *slide, int where);
 /* slk_step_n_slide with slk_step_ekf as the step (see slk_update_ekf_model above; slide may be NULL) */
 int slk_step_n_ekf(slk_filter *f, const slk_traj *t, const int *slide, int where);
+/* ---- per-step consistency records of a trajectory (see slk_nis / slk_get_sigma below).  slk_traj and the three entry
+ *      points above stay as they are; the records are a separate argument, like the slide schedule.
+ *      d == NULL, or every member NULL, is exactly slk_step_n_slide (ekf == 0) / slk_step_n_ekf (ekf != 0).  With
+ *      records, the mean, P, the status bits, the outlier counts and every slk_traj record are bit-identical to the same
+ *      call without d: each step's own launches are unchanged, the records are extra launches beside them.
+ *        nis_hist    [T][B]     slk_nis of step t's update on the PREDICTED state of step t (before any gate)
+ *        logdet_hist [T][B]     its log det S (may be recorded without nis_hist)
+ *        sigma_hist  [T][B][N]  slk_get_sigma(0, N) after step t (after its slide, like mean_hist)
+ *      The fused step kernels never expose their predicted state, so the NIS record comes from a shadow of the step's
+ *      first half: the state is copied device-to-device into a scratch pair of the handle (B (N^2 + Nq) doubles; a
+ *      lower-only P is completed in the copy, the filter's own stays lower-only), slk_predict's launch, the emit-4
+ *      launch and the statistics kernel of slk_nis run on the copy, then the step runs as always.  The shadow predict is
+ *      slk_predict's launch, so nis_hist[t] is bit for bit what slk_predict + slk_nis give on the state before step t (as
+ *      slk_get_state reads it); it agrees with the fused step's internal S to rounding only.  The filter's status
+ *      bits are not touched by the shadow; a filter whose shadow fails (P not positive definite) records NaN.
+ *      Cost: one more predict and one more sigma-point / h(X) / moments pass per step plus the copy of the state: 2.5 x
+ *      an unrecorded step at N = 60, m = 8, B = 4096; sigma_hist alone is one small launch.
+ *      Everything on the handle's stream, no host synchronisation between steps, every reservation before the first
+ *      launch; SLK_HOST: the records come down once at the end.
+ *      SLK_E_INVALID, the filter untouched: ekf != 0 with nis_hist or logdet_hist (the EKF kernels form H P H^T + R
+ *      internally); everything slk_step_n_slide / slk_step_n_ekf refuse. ---- */
+typedef struct slk_traj_diag {
+    double *nis_hist;      /* [T][B]    slk_nis of step t's update, taken on the PREDICTED state of step t */
+    double *logdet_hist;   /* [T][B]    its log det S (needs nothing else; may be set without nis_hist) */
+    double *sigma_hist;    /* [T][B][N] slk_get_sigma(0, N) after step t (after its slide, like mean_hist) */
+} slk_traj_diag;           /* every member NULL = not recorded */
+int slk_step_n_diag(slk_filter *f, const slk_traj *t, const int *slide, int ekf, const slk_traj_diag *d, int where);
 
 /* ---- Tier B (opaque host functors, the reference's boost::bind form:
  *      UsckfUnitTest.cpp:246,284; MsckfUnitTest.cpp:200-205).  The library draws the sigma
@@ -380,6 +407,30 @@ int slk_check_sigma_points(slk_filter *f, double *max_cov_err, double *mean_err,
 int slk_nees(slk_filter *f, const double *truth /*[B][Nq]*/, int t0, int n, double *nees /*[B]*/,
              double *err /*[B][n] or NULL*/, int where);
 int slk_sample_states(slk_filter *f, const double *noise /*[B][S][N]*/, int S, double *out /*[B][S][Nq]*/, int where);
+/* ---- the two consistency statistics that need no ground truth (the reference has no such call).  Both are read-only
+ *      like slk_nees: mean, P, status bits and outlier counts stay as they were.
+ *
+ *      slk_nis: normalised innovation squared of the update slk_update would make with these arguments.  Arguments up
+ *        to r_stride exactly as slk_update_innovation (the same checks and refusals: Z only with SLK_MODEL_EXTERNAL,
+ *        Msckf m <= 32, Usckf any m), both kinds, every N.
+ *        nis [B] = nu^T S^-1 nu, logdet [B] = log det S (NULL = not wanted), with S and nu bit for bit what
+ *        slk_update_innovation emits (all m rows, before any gate).  The Gaussian log-likelihood of the measurement is
+ *        -0.5 (nis + logdet + m log(2 pi)).
+ *        Two launches on the handle's stream: the emit-4 launch of slk_update_innovation into a workspace of the handle
+ *        (B (m^2 + m) doubles, reserved before any launch and kept between calls), then innovation_stats_kernel, which
+ *        factors S with nu as a bordering row: one wave per filter in registers for m <= 30, four waves on slk_nees's
+ *        workspace above (its size at n = m).  Like slk_update_innovation it completes a lower-only P first.
+ *        A non-positive or NaN Cholesky pivot of S gives that filter NaN in both outputs; so does an emission that is
+ *        skipped (P not positive definite, a bad pose index in device-resident parameters) -- and, unlike
+ *        slk_update_innovation, no status bit is set either way.  The call returns SLK_OK, other filters are unaffected.
+ *        SLK_E_INVALID for a NULL nis and for everything slk_update_innovation refuses.
+ *      slk_get_sigma: sigma [B][n], sigma[b][i] = sqrt(P_b(t0 + i, t0 + i)) on the tangent indices [t0, t0 + n) (the
+ *        range rules and errors of slk_nees).  One launch that reads the diagonal only: a lower-only P is not completed
+ *        first and stays lower-only.  A negative or NaN diagonal entry gives NaN for that entry.  `where` other than
+ *        SLK_HOST / SLK_DEVICE is SLK_E_INVALID. ---- */
+int slk_nis(slk_filter *f, int model, const double *params, int p_stride, const double *Z, const double *z, int m,
+            const double *R, int r_stride, double *nis /*[B]*/, double *logdet /*[B] or NULL*/, int where);
+int slk_get_sigma(slk_filter *f, int t0, int n, double *sigma /*[B][n]*/, int where);
 
 /* ---- arithmetic of the covariance rebuild (Msckf.hpp:665 -> :574-589): SLK_PREC_F64 (default, the
  *      parity path), SLK_PREC_F32 (fp32 MFMA) or SLK_PREC_BF16 (bf16 operands, fp32 accumulation).

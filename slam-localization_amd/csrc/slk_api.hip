@@ -72,6 +72,8 @@ struct slk_filter {
     Stage ws_lin;                 // EKF update from a registered model: zmean, H of the linearisation and its skip flags
     Stage ws_cons;                // slk_nees / slk_sample_states workspace (consistency_ws), allocated on first use
     Stage st_truth, st_rec;       // slk_step_n (host route): the truths of all steps, the device copy of the records
+    Stage ws_nis;                 // slk_nis / the NIS records of slk_step_n_diag: S and nu of the emission, the outputs of a
+                                  // host call, the status words the shadow launches may set (nis_ws)
     // Msckf rotation-item descriptors, one table per window length k the handle has run (a sliding window alternates
     // between k and k + 1: the tables stay, so the steady state allocates and synchronises nothing)
     struct Rtab { unsigned long long *dev = nullptr; std::vector<unsigned long long> host; };
@@ -173,7 +175,7 @@ void slk_destroy(slk_filter *f)
     (void)hipSetDevice(f->cfg.device);
     (void)hipStreamSynchronize(f->stream);
     Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_X, &f->st_Z, &f->st_tmpP, &f->st_tmpM,
-                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_cons, &f->st_truth, &f->st_rec};
+                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_cons, &f->st_truth, &f->st_rec, &f->ws_nis};
     for (Stage *s : st) if (s->p) (void)hipFree(s->p);
     for (auto &kv : f->rtabs) if (kv.second.dev) (void)hipFree(kv.second.dev);
     if (f->d_mean) (void)hipFree(f->d_mean);
@@ -1566,6 +1568,129 @@ int slk_sample_states(slk_filter *f, const double *noise, int S, double *out, in
     return SLK_OK;
 }
 
+// ---- innovation consistency (slk_nis) and standard deviations (slk_get_sigma)
+// ws_nis (doubles): SI [B][m * m + m] of the emit-4 launch, then nis, logdet [2][B] (the outputs of a host call), then
+// one status word and one outlier count per filter for the launches that must not touch the filter's own (never
+// initialised, never read: every kernel only ORs into its status word and stores its outlier count)
+struct NisWs { size_t si, out, status, outliers, total; };
+static NisWs nis_ws(size_t B, int m)
+{
+    NisWs w;
+    const size_t words = (B * sizeof(int) + sizeof(double) - 1) / sizeof(double);
+    w.si = 0; w.out = B * ((size_t)m * m + m); w.status = w.out + 2 * B; w.outliers = w.status + words;
+    w.total = w.outliers + words;
+    return w;
+}
+
+// what the emit-4 launch of this shape checks and reserves beyond the step's own reservations (prepare_step), and the
+// workspaces of innovation_stats_kernel: everything of slk_nis that can fail, before any launch
+static int reserve_nis(slk_filter *f, int m)
+{
+    const Lay &L = f->lay;
+    const size_t B = (size_t)f->B;
+    int rc = stage_reserve(f, f->ws_nis, nis_ws(B, m).total);
+    if (rc) return rc;
+    if (m > STATS_ROWS_MAX) { rc = stage_reserve(f, f->ws_cons, B * consistency_ws(m).total); if (rc) return rc; }
+    if (L.kind == SLK_USCKF && m <= MAXM && L.N <= 96
+        && (size_t)carve_usckf(L.N, L.Nq, m, (L.N + 15) / 16).total * sizeof(double) > 160 * 1024) {
+        g_err = "state too large for the LDS-resident kernel"; return SLK_E_UNSUPPORTED;
+    }
+    return SLK_OK;
+}
+
+// The emit-4 launch of `a` (update fields filled, any gate) into ws_nis, then innovation_stats_kernel: dn / dl [B]
+// (device, either may be null).  SI is filled with NaN first: a filter whose emission is skipped (its P does not factor,
+// a bad pose index in device parameters) gets NaN statistics.  The status word such a launch sets goes to ws_nis: the
+// filter's own status bits and outlier counts stay as they were.  reserve_nis has run.
+static int launch_nis(slk_filter *f, KArgs a, double *dn, double *dl)
+{
+    const size_t B = (size_t)f->B;
+    const int m = a.m;
+    const NisWs w = nis_ws(B, m);
+    double *si = f->ws_nis.p + w.si;
+    HIPCHECK(hipMemsetAsync(si, 0xff, B * ((size_t)m * m + m) * sizeof(double), f->stream));
+    a.do_predict = 0; a.gate = 0; a.emit = 4; a.Xout = si;
+    a.status = reinterpret_cast<int *>(f->ws_nis.p + w.status);
+    a.outliers = reinterpret_cast<unsigned *>(f->ws_nis.p + w.outliers);
+    int rc = launch(f, a);
+    if (rc) return rc;
+#ifdef SLK_DEV_N60
+    g_err = "development build: no consistency kernels"; return SLK_E_UNSUPPORTED;
+#else
+    hipLaunchKernelGGL(innovation_stats_kernel, dim3(f->B), dim3(m <= STATS_ROWS_MAX ? 64 : 256), 0, f->stream,
+                       (const double *)si, m, dn, dl, f->ws_cons.p);
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+#endif
+}
+
+int slk_nis(slk_filter *f, int model, const double *params, int p_stride, const double *Z, const double *z, int m,
+            const double *R, int r_stride, double *nis, double *logdet, int where)
+{
+    if (!f || !nis) return SLK_E_INVALID;
+    if ((model == SLK_MODEL_EXTERNAL) != (Z != nullptr)) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    int rc = check_update(f, model, params, p_stride, z, m, R, r_stride, where);
+    if (rc) return rc;
+    rc = reserve_nis(f, m);
+    if (rc) return rc;
+    KArgs a;
+    base_args(f, a);
+    rc = fill_update(f, a, model, params, p_stride, z, m, R, r_stride, 0, where);
+    if (rc) return rc;
+    if (Z) { rc = stage_in(f, f->st_Z, Z, (size_t)f->B * (2 * f->lay.N + 1) * m, where, &a.Zext); if (rc) return rc; }
+    const size_t B = (size_t)f->B;
+    double *dn = nis, *dl = logdet;
+    if (where == SLK_HOST) {
+        dn = f->ws_nis.p + nis_ws(B, m).out;
+        dl = logdet ? dn + B : nullptr;
+    }
+    rc = launch_nis(f, a, dn, dl);
+    if (rc) return rc;
+    if (where == SLK_HOST) {
+        HIPCHECK(hipMemcpyAsync(nis, dn, B * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (logdet) HIPCHECK(hipMemcpyAsync(logdet, dl, B * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        HIPCHECK(hipStreamSynchronize(f->stream));
+    }
+    return SLK_OK;
+}
+
+// sigma [B][n] (device) of the resident P: the diagonal only, so a lower-only covariance is read as it is
+static int launch_sigma(slk_filter *f, int t0, int n, double *dsigma)
+{
+#ifdef SLK_DEV_N60
+    (void)t0; (void)n; (void)dsigma;
+    g_err = "development build: no consistency kernels"; return SLK_E_UNSUPPORTED;
+#else
+    const size_t total = (size_t)f->B * n;
+    hipLaunchKernelGGL(sigma_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double *)f->d_P,
+                       f->B, f->lay.N, t0, n, dsigma);
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+#endif
+}
+
+int slk_get_sigma(slk_filter *f, int t0, int n, double *sigma, int where)
+{
+    if (!f || !sigma || t0 < 0 || n < 1 || n > f->lay.N - t0) return SLK_E_INVALID;
+    if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t total = (size_t)f->B * n;
+    double *ds = sigma;
+    if (where == SLK_HOST) {
+        int rc = stage_reserve(f, f->st_tmpM, total);
+        if (rc) return rc;
+        ds = f->st_tmpM.p;
+    }
+    int rc = launch_sigma(f, t0, n, ds);
+    if (rc) return rc;
+    if (where == SLK_HOST) {
+        HIPCHECK(hipMemcpyAsync(sigma, ds, total * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        HIPCHECK(hipStreamSynchronize(f->stream));
+    }
+    return SLK_OK;
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------- multi-step trajectories (slk_step_n)
@@ -1615,10 +1740,15 @@ extern "C" {
 // slk_step_n, slk_step_n_slide and slk_step_n_ekf: slide == NULL is slk_step_n; slide[t] >= 0 slides the window after
 // step t, before that step's records.  ekf: every step is slk_step_ekf (predict, linearisation, EKF kernel) instead of
 // slk_step; the checks of the measurement side and the reservations are those of slk_step_ekf, everything else is shared.
-static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where, bool ekf = false)
+// d (slk_step_n_diag): extra records beside the steps; the launches of every step are those of a call without d.
+static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where, bool ekf = false,
+                  const slk_traj_diag *d = nullptr)
 {
     if (!f || !t || t->T < 1 || t->mmodel == SLK_MODEL_EXTERNAL) return SLK_E_INVALID;
     if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
+    const bool want_nis = d && d->nis_hist, want_logdet = d && d->logdet_hist, want_sigma = d && d->sigma_hist;
+    const bool want_innov = want_nis || want_logdet;
+    if (ekf && want_innov) { g_err = "slk_step_n_diag: no NIS records of the EKF step"; return SLK_E_INVALID; }
     const int T = t->T, m = t->m;
     const size_t B = (size_t)f->B, Nq = (size_t)f->lay.Nq;
     // ---- every check, before anything is reserved or launched
@@ -1678,9 +1808,11 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where,
     const size_t sth = want_nees ? span(t->truth_tstride, B * Nq) : 0;
     const size_t nmean = t->mean_hist ? (size_t)T * B * Nq : 0, nnees = want_nees ? (size_t)T * B : 0;
     const size_t nout = t->outliers_hist ? ((size_t)T * B * sizeof(unsigned) + sizeof(double) - 1) / sizeof(double) : 0;
+    const size_t nnis = want_nis ? (size_t)T * B : 0, nlogdet = want_logdet ? (size_t)T * B : 0;
+    const size_t nsigma = want_sigma ? (size_t)T * B * f->lay.N : 0;
     if (where == SLK_HOST) {
         Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_truth, &f->st_rec};
-        const size_t n[] = {su, sq, sp, sz, sr, sth, nmean + nnees + nout};
+        const size_t n[] = {su, sq, sp, sz, sr, sth, nmean + nnees + nout + nnis + nlogdet + nsigma};
         for (int i = 0; i < 7; ++i) if (n[i]) { rc = stage_reserve(f, *st[i], n[i]); if (rc) return rc; }
     }
     rc = ekf ? reserve_ekf_model(f, m) : prepare_step(f, a);     // (a predict-only launch reserves nothing)
@@ -1688,6 +1820,12 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where,
     if (any_slide) { rc = reserve_slide(f); if (rc) return rc; }
     const bool nees_rows = want_nees && t->nees_n <= NEES_ROWS_MAX;     // the one-wave record kernel: no workspace
     if (want_nees && !nees_rows) { rc = stage_reserve(f, f->ws_cons, B * consistency_ws(t->nees_n).total); if (rc) return rc; }
+    if (want_innov) {                                           // the shadow state and what slk_nis reserves
+        rc = stage_reserve(f, f->st_tmpP, B * (size_t)f->lay.N * f->lay.N);
+        if (!rc) rc = stage_reserve(f, f->st_tmpM, B * Nq);
+        if (!rc) rc = reserve_nis(f, m);
+        if (rc) return rc;                                      // (ws_cons only grows: it now serves both kernels)
+    }
 #ifdef SLK_DEV_N60
     g_err = "development build: no trajectory route"; return SLK_E_UNSUPPORTED;
 #else
@@ -1695,6 +1833,8 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where,
     const double *du = t->u, *dq = t->Q, *dp = np ? t->params : nullptr, *dz = t->z, *dr = t->R, *dth = t->truth;
     double *dmean = t->mean_hist, *dnees = t->nees_hist;
     unsigned *dout = t->outliers_hist;
+    double *dnis = want_nis ? d->nis_hist : nullptr, *dlogdet = want_logdet ? d->logdet_hist : nullptr;
+    double *dsigma = want_sigma ? d->sigma_hist : nullptr;
     if (where == SLK_HOST) {
         auto up = [&](Stage &s, const double *src, size_t n, const double **out) -> int {
             if (!n) return SLK_OK;
@@ -1708,6 +1848,10 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where,
         dmean = t->mean_hist ? f->st_rec.p : nullptr;
         dnees = want_nees ? f->st_rec.p + nmean : nullptr;
         dout = t->outliers_hist ? reinterpret_cast<unsigned *>(f->st_rec.p + nmean + nnees) : nullptr;
+        double *drec = f->st_rec.p + nmean + nnees + nout;
+        dnis = want_nis ? drec : nullptr;
+        dlogdet = want_logdet ? drec + nnis : nullptr;
+        dsigma = want_sigma ? drec + nnis + nlogdet : nullptr;
     }
     a.u = du; a.Q = dq;
     if (!ekf) { a.mp = dp; a.z = dz; a.R = dr; }
@@ -1720,6 +1864,32 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where,
         const double *mps = dp ? dp + (size_t)s * t->p_tstride : nullptr;
         const double *zs = dz + (size_t)s * t->z_tstride, *rs = dr + (size_t)s * t->r_tstride;
         if (!ekf) { as.mp = mps; as.z = zs; as.R = rs; }
+        if (want_innov) {
+            // The NIS record of the step, from a shadow of its first half: the state copied into the handle's scratch
+            // pair (a lower-only P completed THERE, not in the filter), slk_predict's launch and slk_nis's two launches on
+            // the copy.  The filter, its status bits and the lower-only bookkeeping of its P stay out of it.
+            const size_t N = (size_t)f->lay.N;
+            const bool stale = f->upper_stale;
+            HIPCHECK(hipMemcpyAsync(f->st_tmpM.p, f->d_mean, B * Nq * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
+            HIPCHECK(hipMemcpyAsync(f->st_tmpP.p, f->d_P, B * N * N * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
+            if (stale) {
+                hipLaunchKernelGGL(slk_mirror_upper_kernel, dim3(f->B), dim3(256), 0, f->stream, f->st_tmpP.p, f->lay.N);
+                HIPCHECK(hipGetLastError());
+            }
+            const NisWs w = nis_ws(B, m);
+            KArgs sh = as;
+            sh.mean = f->st_tmpM.p; sh.P = f->st_tmpP.p;
+            sh.status = reinterpret_cast<int *>(f->ws_nis.p + w.status);
+            sh.outliers = reinterpret_cast<unsigned *>(f->ws_nis.p + w.outliers);
+            KArgs pr = sh;                                     // the predict-only call: no measurement fields
+            pr.do_update = 0; pr.mm = 0; pr.mp = nullptr; pr.mp_stride = 0; pr.z = nullptr; pr.m = 0;
+            pr.R = nullptr; pr.r_stride = 0; pr.gate = 0;
+            f->upper_stale = false;                            // (the copy is complete: nothing of the filter to mirror)
+            rc = launch(f, pr);
+            if (!rc) rc = launch_nis(f, sh, dnis ? dnis + (size_t)s * B : nullptr, dlogdet ? dlogdet + (size_t)s * B : nullptr);
+            f->upper_stale = stale;
+            if (rc) return rc;
+        }
         rc = launch(f, as);                                    // (ekf: the predict-only launch)
         if (rc) return rc;
         if (ekf) { rc = launch_ekf_model(f, mps, t->p_stride, zs, m, rs, t->r_stride, t->gate); if (rc) return rc; }
@@ -1741,12 +1911,16 @@ static int step_n(slk_filter *f, const slk_traj *t, const int *slide, int where,
                                dnees + (size_t)s * B, (double *)nullptr, f->ws_cons.p);
             HIPCHECK(hipGetLastError());
         }
+        if (dsigma) { rc = launch_sigma(f, 0, f->lay.N, dsigma + (size_t)s * B * f->lay.N); if (rc) return rc; }
     }
     if (where == SLK_HOST) {                                    // one download of the records
         if (t->mean_hist) HIPCHECK(hipMemcpyAsync(t->mean_hist, dmean, nmean * sizeof(double), hipMemcpyDeviceToHost, f->stream));
         if (want_nees) HIPCHECK(hipMemcpyAsync(t->nees_hist, dnees, nnees * sizeof(double), hipMemcpyDeviceToHost, f->stream));
         if (t->outliers_hist)
             HIPCHECK(hipMemcpyAsync(t->outliers_hist, dout, (size_t)T * B * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream));
+        if (want_nis) HIPCHECK(hipMemcpyAsync(d->nis_hist, dnis, nnis * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (want_logdet) HIPCHECK(hipMemcpyAsync(d->logdet_hist, dlogdet, nlogdet * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (want_sigma) HIPCHECK(hipMemcpyAsync(d->sigma_hist, dsigma, nsigma * sizeof(double), hipMemcpyDeviceToHost, f->stream));
         HIPCHECK(hipStreamSynchronize(f->stream));
     }
     return SLK_OK;
@@ -1758,6 +1932,11 @@ int slk_step_n(slk_filter *f, const slk_traj *t, int where) { return step_n(f, t
 int slk_step_n_slide(slk_filter *f, const slk_traj *t, const int *slide, int where) { return step_n(f, t, slide, where); }
 
 int slk_step_n_ekf(slk_filter *f, const slk_traj *t, const int *slide, int where) { return step_n(f, t, slide, where, true); }
+
+int slk_step_n_diag(slk_filter *f, const slk_traj *t, const int *slide, int ekf, const slk_traj_diag *d, int where)
+{
+    return step_n(f, t, slide, where, ekf != 0, d);
+}
 
 struct slk_adaptive {
     int B, device;

@@ -39,6 +39,20 @@ __global__ void nees_kernel(Lay L, const double *mean, const double *P, const do
 __global__ void sample_states_kernel(Lay L, const double *mean, const double *P, const double *noise, int S, double *out,
                                      double *wsbase);
 
+// Innovation consistency (slk_nis) and standard deviations (slk_get_sigma); slk_step_n_diag records both per step.
+//   NIS:   SI [B][m * m + m] is what an emit-4 launch wrote (S column-major, then the innovation nu).  The bordered
+//          (m + 1) x (m + 1) matrix [[S, .], [nu^T, BIG]] is factored as for the NEES: its last row is (Ls^-1 nu)^T, so
+//          nis = |Ls^-1 nu|^2, and log det S = 2 sum log Ls_ii comes from the same pivots.  m <= STATS_ROWS_MAX: ONE wave
+//          per filter (launched with 64 threads), chol_rows in registers, no workspace (the form of nees_rows_kernel);
+//          above that four waves (256 threads) through chol_blocked_mem on the consistency_ws(m) workspace (the form of
+//          nees_kernel).  Reads the lower triangle of S.  A non-positive or NaN pivot gives NaN in both outputs (an
+//          emission that was skipped leaves the NaN the host filled SI with: the same answer).
+//   sigma: sqrt of the diagonal of P on tangent indices [t0, t0 + n), one thread per number; a negative or NaN entry
+//          gives NaN.  Nothing but the diagonal is read.
+constexpr int STATS_ROWS_MAX = 30;     // m + 1 <= 31 rows of chol_rows
+__global__ void innovation_stats_kernel(const double *SI, int m, double *nis, double *logdet, double *wsbase);
+__global__ void sigma_kernel(const double *P, int B, int N, int t0, int n, double *sigma);
+
 #ifdef SLK_CONSISTENCY_UNIT
 // The SO(3) arithmetic takes its LEAF forms (the libm routes inlined): a call from these kernels to the out-of-line
 // routes would change what the compiler infers for those functions, and with it the code of every existing kernel that
@@ -151,6 +165,64 @@ __global__ __launch_bounds__(256) void sample_states_kernel(Lay L, const double 
         }
         __syncthreads();
     }
+}
+
+// nis [B], logdet [B] (either may be null) from SI [B][m * m + m]; grid B, 64 threads for m <= STATS_ROWS_MAX, else 256
+__global__ __launch_bounds__(256) void innovation_stats_kernel(const double *SI, int m, double *nis, double *logdet,
+                                                               double *wsbase)
+{
+    __shared__ __attribute__((aligned(16))) double cb[4 * 34 + 152];     // chol_blocked_mem: diagonal tile factor, pivots
+    __shared__ double Lr[31 * 32 / 2];                                   // the one-wave form's packed factor
+    __shared__ double red[4];
+    __shared__ int ish[1];
+    const int bidx = blockIdx.x, tid = threadIdx.x;
+    const double *S = SI + (size_t)bidx * (m * m + m), *nu = S + m * m;
+    // init(i, j), i >= j for the blocked form; chol_rows hands any (row, column): the lower triangle of S either way
+    auto init = [&](int i, int j) -> double {
+        if (i < m) return j < m ? S[max(i, j) + m * min(i, j)] : 0.0;
+        return j < m ? nu[j] : 0x1p1000;
+    };
+    if (m <= STATS_ROWS_MAX) {
+        const int fail = chol_rows<31>(Lr, m + 1, tid, init);
+        double s2 = 0.0, ld = 0.0;
+        for (int j = 0; j < m; ++j) {
+            const double y = Lr[pk(m + 1, m, j)];
+            s2 = fma(y, y, s2);
+            ld += log(Lr[pk(m + 1, j, j)]);
+        }
+        if (tid == 0) {
+            if (nis) nis[bidx] = fail >= 0 ? __builtin_nan("") : s2;
+            if (logdet) logdet[bidx] = fail >= 0 ? __builtin_nan("") : 2.0 * ld;
+        }
+        return;
+    }
+    const ConsWs w = consistency_ws(m);
+    double *ws = wsbase + (size_t)bidx * w.total;
+    double *Lp = ws + w.Lp, *panel = ws + w.panel;
+    const int fail = chol_blocked_mem<256>(Lp, m + 1, panel, cb, &ish[0], tid, init);
+    double s2 = 0.0, ld = 0.0;
+    for (int j = tid; j < m; j += 256) {
+        const double y = Lp[pk(m + 1, m, j)];
+        s2 = fma(y, y, s2);
+        ld += fail >= 0 ? 0.0 : log(Lp[pk(m + 1, j, j)]);
+    }
+    const double r = block_sum_256(s2, red, tid);
+    __syncthreads();                                                     // (red is reused)
+    const double l = block_sum_256(ld, red, tid);
+    if (tid == 0) {
+        if (nis) nis[bidx] = fail >= 0 ? __builtin_nan("") : r;
+        if (logdet) logdet[bidx] = fail >= 0 ? __builtin_nan("") : 2.0 * l;
+    }
+}
+
+// sigma [B][n] = sqrt(P_b(t0 + i, t0 + i)); grid ceil(B n / 256), 256 threads
+__global__ __launch_bounds__(256) void sigma_kernel(const double *P, int B, int N, int t0, int n, double *sigma)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)B * n) return;
+    const size_t b = e / n;
+    const int i = t0 + (int)(e - b * n);
+    sigma[e] = sqrt(P[b * (size_t)N * N + (size_t)i * (N + 1)]);        // (negative or NaN: NaN)
 }
 
 #endif // SLK_CONSISTENCY_UNIT

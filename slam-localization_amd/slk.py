@@ -35,6 +35,7 @@ EXPORTS = [
     "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix", "slk_nees",
     "slk_sample_states", "slk_step_n", "slk_step_n_slide", "slk_msckf_slide",
     "slk_ekf_linearize", "slk_update_ekf_model", "slk_step_ekf", "slk_step_n_ekf",
+    "slk_nis", "slk_get_sigma", "slk_step_n_diag",
 ]
 
 
@@ -59,6 +60,11 @@ class Traj(C.Structure):
                 ("mean_hist", C.c_void_p), ("outliers_hist", C.c_void_p),
                 ("truth", C.c_void_p), ("truth_tstride", C.c_longlong), ("nees_t0", C.c_int), ("nees_n", C.c_int),
                 ("nees_hist", C.c_void_p)]
+
+
+class TrajDiag(C.Structure):
+    """struct slk_traj_diag of include/slk.h"""
+    _fields_ = [("nis_hist", C.c_void_p), ("logdet_hist", C.c_void_p), ("sigma_hist", C.c_void_p)]
 
 
 _lib = None
@@ -123,6 +129,9 @@ def load_library(path=None):
     lib.slk_update_ekf_model.argtypes = [vp, ip, vp, ip, vp, ip, vp, ip, ip, ip]
     lib.slk_step_ekf.argtypes = [vp, ip, vp, ip, vp, ip, ip, vp, ip, vp, ip, vp, ip, ip, ip]
     lib.slk_step_n_ekf.argtypes = [vp, C.POINTER(Traj), vp, ip]
+    lib.slk_nis.argtypes = [vp, ip, vp, ip, vp, vp, ip, vp, ip, vp, vp, ip]
+    lib.slk_get_sigma.argtypes = [vp, ip, ip, vp, ip]
+    lib.slk_step_n_diag.argtypes = [vp, C.POINTER(Traj), vp, ip, C.POINTER(TrajDiag), ip]
     if path is None:
         _lib = lib
     return lib
@@ -370,7 +379,7 @@ class _FilterBatch:
                "slk_step")
 
     def step_n(self, pmodel, u, Q, z, mmodel, params, R, gate=None, truth=None, nees_range=None, record_mean=False,
-               record_outliers=False, slide=None, update="ukf"):
+               record_outliers=False, slide=None, update="ukf", diag=()):
         """T fused steps in one call (slk_step_n): the same results as T calls of step() with the inputs of each step.
         update="ekf" (Msckf, slk_step_n_ekf): every step is step_ekf() instead of step() -- predict, then the EKF update
         from the registered model mmodel linearised on the device (N <= m <= 512 rows); the arguments, the records and
@@ -383,7 +392,14 @@ class _FilterBatch:
         -> device route, device tensors out.
         slide (slk_step_n_slide): an int d slides the window after every step (drop clone d, clone the current pose),
         or a length-T sequence with -1 (no slide after that step) or d; the records of a step are taken after its
-        slide.  The results are those of step() followed by drop_clone(d) + clone_pose() where d >= 0."""
+        slide.  The results are those of step() followed by drop_clone(d) + clone_pose() where d >= 0.
+        diag (slk_step_n_diag): any of "nis", "logdet", "sigma" adds the records "nis" [T, B] (nis() of step t's update
+        on the predicted state of step t), "logdet" [T, B] (its log det S) and "sigma" [T, B, N] (sigma() after step t);
+        the state and every other record are bit-identical to the call without diag.  "nis" / "logdet" need
+        update="ukf".  The default leaves the call what it was."""
+        diag = (diag,) if isinstance(diag, str) else tuple(diag)
+        if any(x not in ("nis", "logdet", "sigma") for x in diag):
+            raise SlkError(f"step_n: diag takes 'nis', 'logdet', 'sigma', got {diag!r}")
         if update not in ("ukf", "ekf"):
             raise SlkError(f"step_n: update must be 'ukf' or 'ekf', got {update!r}")
         T = int(z.shape[0])
@@ -428,6 +444,8 @@ class _FilterBatch:
                 out["outliers"] = torch.empty((T, B), dtype=torch.uint32, device=dev)
             if truth is not None:
                 out["nees"] = torch.empty((T, B), dtype=torch.float64, device=dev)
+            for x in diag:
+                out[x] = torch.empty((T, B, self.N) if x == "sigma" else (T, B), dtype=torch.float64, device=dev)
             ptr = {k: v.data_ptr() for k, v in out.items()}
         else:
             if record_mean:
@@ -436,11 +454,17 @@ class _FilterBatch:
                 out["outliers"] = np.empty((T, B), dtype=np.uint32)
             if truth is not None:
                 out["nees"] = np.empty((T, B))
+            for x in diag:
+                out[x] = np.empty((T, B, self.N) if x == "sigma" else (T, B))
             ptr = {k: v.ctypes.data for k, v in out.items()}
         tr.mean_hist, tr.outliers_hist, tr.nees_hist = ptr.get("mean"), ptr.get("outliers"), ptr.get("nees")
         if ta is not None:
             tr.truth, tr.truth_tstride, tr.nees_t0, tr.nees_n = ta[0], ta[2], t0, n
-        if update == "ekf":
+        if diag:
+            dg = TrajDiag(ptr.get("nis"), ptr.get("logdet"), ptr.get("sigma"))
+            _check(self._lib.slk_step_n_diag(self._h, C.byref(tr), sched.ctypes.data if sched is not None else None,
+                                             int(update == "ekf"), C.byref(dg), where), "slk_step_n_diag")
+        elif update == "ekf":
             _check(self._lib.slk_step_n_ekf(self._h, C.byref(tr), sched.ctypes.data if sched is not None else None, where),
                    "slk_step_n_ekf")
         elif sched is None:
@@ -544,6 +568,54 @@ class _FilterBatch:
         if where == DEVICE:
             self.sync()                                        # torch may read the outputs on any stream
         return (out, err) if error else out
+
+    def nis(self, z, model, params, R, logdet=False):
+        """Normalised innovation squared nu^T S^-1 nu [B] of the update that update(z, model, params, R) would make (all
+        rows, before any gate); the filter is not modified.  logdet=True returns (nis, log det S): the Gaussian
+        log-likelihood of z is -0.5 * (nis + logdet + m * log(2 pi)).  An S that is not positive definite gives NaN for
+        that filter.  Arguments as update() takes them; numpy in -> numpy out, torch device tensors in -> torch device
+        tensors out (torch's stream is synchronised before the call, the handle's after it)."""
+        m = int(z.shape[-1])
+        pa = _rows(params, self.B, _np(model, m)) if _np(model, m) else _Arg(None, 0, None, None)
+        za, ra = _zrows(z, self.B, m), _mat(R, self.B, m)
+        return self._nis(model, pa, None, za, m, ra, logdet, _where(pa, za, ra), z)
+
+    def _nis(self, model, pa, Zptr, za, m, ra, logdet, where, ztensor):
+        B = self.B
+        if where == DEVICE:
+            import torch
+            dev = ztensor.device
+            torch.cuda.current_stream(dev).synchronize()      # (the handle's stream does not wait for torch's)
+            out = torch.empty(B, dtype=torch.float64, device=dev)
+            ld = torch.empty(B, dtype=torch.float64, device=dev) if logdet else None
+            optr, lptr = out.data_ptr(), (ld.data_ptr() if logdet else None)
+        else:
+            out = np.empty(B)
+            ld = np.empty(B) if logdet else None
+            optr, lptr = out.ctypes.data, (ld.ctypes.data if logdet else None)
+        _check(self._lib.slk_nis(self._h, model, pa.ptr, pa.stride, Zptr, za.ptr, m, ra.ptr, ra.stride, optr, lptr, where),
+               "slk_nis")
+        if where == DEVICE:
+            self.sync()                                        # torch may read the outputs on any stream
+        return (out, ld) if logdet else out
+
+    def nis_functor(self, z, h, R, logdet=False):
+        """nis() with an arbitrary Python callable h: full state [Nq] -> z [m], applied to the sigma points on the host
+        (the Tier-B form, as update_functor)."""
+        X = self.update_sigma_points()
+        Z = np.ascontiguousarray([[h(x) for x in Xb] for Xb in X], dtype=np.float64)
+        m = Z.shape[-1]
+        za, ra = _zrows(np.asarray(z, dtype=np.float64), self.B, m), _mat(np.asarray(R), self.B, m)
+        return self._nis(MODEL_EXTERNAL, _Arg(None, 0, None, None), Z.ctypes.data, za, m, ra, logdet, HOST, None)
+
+    def sigma(self, t0=0, n=None):
+        """Standard deviations sqrt(diag P) [B, n] on the tangent indices [t0, t0 + n) (default: to N), read from the
+        diagonal on the device: P is not downloaded and a lower-only P is not completed.  A negative or NaN diagonal
+        entry gives NaN."""
+        n = self.N - int(t0) if n is None else int(n)
+        out = np.empty((self.B, max(n, 0)))
+        _check(self._lib.slk_get_sigma(self._h, int(t0), n, out.ctypes.data, HOST), "slk_get_sigma")
+        return out
 
     def sample_states(self, noise):
         """Gaussian draws from every filter's own (mu, P): out [B, S, Nq] = mu [+] (L n) for noise [B, S, N] (e.g. standard
