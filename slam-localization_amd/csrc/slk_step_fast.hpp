@@ -16,8 +16,9 @@
 //     the rotation rows of the tiled factor (so that O = the factor array) and the even parts minus the centre deviation
 //     into a k-step-major array E^ in the index space of the rotation rows:
 //         P+ = O O^T + E E^T + 1/2 d0 d0^T = O O^T + E^ E^^T + p d0^T + d0 p^T,   p = sum_j e^_j + (N + 1/2) / 2 d0,
-//     O and E^ are zero beyond column t + 2 of row t: tile column J needs the k-steps 0 .. 4 J + 3 only (79 + 83 MFMAs
-//     instead of 150 + 48 with gathers), one wave per tile column, no cross-wave reduction;
+//     O and E^ are zero beyond column t + 2 of row t: tile column J of O O^T needs the k-steps 0 .. 4 J + 3 only, one wave
+//     per tile column, no cross-wave reduction; E^ E^^T is formed in the rotation-row space (three 16 x 16 tiles, 83 + 37
+//     MFMAs at k = 8) and added where the tiles leave for memory;
 //   * tiles leave from the accumulators (mirror triangle) and through a private LDS transpose (lower triangle).
 // Anything rare -- failed factorisation, rotation column beyond pi, non-SPD innovation covariance, every block gated out,
 // an indefinite downdate, a mean that needs more than 64 rounds, other models / gate modes -- returns false BEFORE the
@@ -399,46 +400,101 @@ __device__ __forceinline__ void ldm_product_tiled(double *Lt, const double *dZi,
     __syncthreads();
 }
 
-// One tile column J of P+ = O O^T + E^ E^^T (k-steps 0 .. 4 J + 3; tile column 0 also the step that holds row 15's columns
-// 16 / 17): acc[I - J] += frag(I) frag(J)^T.
+// The even-part product EE = E^ E^^T in the index space of the rotation rows, where E^ is stored: 32 x 32 (27 rows at k = 8),
+// three lower 16 x 16 tiles (one when every rotation row is below 16, k = 4).  Row rho of E^ is zero beyond column
+// toff(block) + 2, which bounds the k-steps of the tiles with rows below 16.  The result goes to LDS as a full symmetric
+// matrix ee[32][EES] (padding rows / columns exact zeros) and is added where the tiles of P+ leave for memory.
+template <int K> struct FastEE {
+    using F = FastShape<K>;
+    static constexpr int EES = 40;                               // row stride: rows g, g + 1 of a store land 16 banks apart
+    static constexpr int NTE = F::NROT > 16 ? 2 : 1;
+    static constexpr int PAD = 16 * NTE - 1;                     // an all-zero row / column of E^ inside the published tiles
+    static constexpr int BLO = F::NSO3 - 1 < 5 ? F::NSO3 - 1 : 5;   // last block with a row below 16 (rho = 3 b)
+    static constexpr int CLO = (BLO ? 9 + 6 * BLO : 3) + 3;      // its columns end here
+    static constexpr int KS0 = ((CLO + 3) / 4 < F::NKS) ? (CLO + 3) / 4 : F::NKS;   // k-steps of the tiles (0, 0), (1, 0)
+    static constexpr int KS1 = F::NKS;                           // ... of tile (1, 1)
+    // the wave of a tile: the O part gives the waves 20 / 24 / 24 / 15 MFMAs at k = 8 and wave 1 has the second round of
+    // the mean loop, so (0, 0) -> wave 0, (1, 0) -> wave 2, (1, 1) -> wave 3
+    __host__ __device__ static constexpr int wave_of(int hi, int hj) { return hi == 0 ? 0 : (hj == 0 ? 2 : 3); }
+};
+static_assert(32 * FastEE<8>::EES <= FastShape<4>::USZ, "EE fits the union region");
+
+// tile (HI, HJ) of EE from the fragments of E^: a row-rho fragment of k-step ks is Et[ks * 128 + (rho >> 4) * 64 + lane]
+template <int K, int HI, int HJ>
+__device__ __forceinline__ d4 fast_ee_tile(const double *Et, int lane)
+{
+    constexpr int KE = HJ == 0 ? FastEE<K>::KS0 : FastEE<K>::KS1;
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < KE; ++ks) {
+        const double fj = Et[ks * 128 + HJ * 64 + lane];
+        const double fi = HI == HJ ? fj : Et[ks * 128 + HI * 64 + lane];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fi, fj, acc, 0, 0, 0);
+    }
+    return acc;
+}
+// acc[r] of lane (c, g) = EE(16 HI + g + 4 r, 16 HJ + c); an off-diagonal tile in both orientations
+template <int K, int HI, int HJ>
+__device__ __forceinline__ void fast_ee_publish(double *ee, int lane, const d4 &acc)
+{
+    constexpr int EES = FastEE<K>::EES;
+    const int c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        ee[(16 * HI + g + 4 * r) * EES + 16 * HJ + c] = acc[r];
+        if (HI != HJ) ee[(16 * HJ + c) * EES + 16 * HI + g + 4 * r] = acc[r];
+    }
+}
+
+// rotation-row indices of the tangent rows 16 I + G + 4 r (r = 0 .. 3), one byte each (PAD, an all-zero row of EE, for
+// vector rows and padding): the rows a lane of group G = lane >> 4 holds in the accumulator of a tile of row block I
+template <int K> __host__ __device__ constexpr unsigned fast_rho_pack(int I, int G)
+{
+    constexpr int N = FastShape<K>::N, PAD = FastEE<K>::PAD;
+    unsigned w = 0;
+    for (int r = 0; r < 4; ++r) {
+        const int t = 16 * I + G + 4 * r;
+        int rho = PAD;
+        if (t < N) {
+            if (t < 12) rho = (t >= 3 && t < 6) ? t - 3 : PAD;
+            else { const int cc = (t - 12) / 6, q = (t - 12) - 6 * cc; rho = q >= 3 ? 3 * cc + q : PAD; }
+        }
+        w |= (unsigned)rho << (8 * r);
+    }
+    return w;
+}
+
+// One tile column J of O O^T (k-steps 0 .. 4 J + 3; tile column 0 also the step that holds row 15's columns 16 / 17):
+// acc[I - J] += frag(I) frag(J)^T.
 template <int K, int J>
-__device__ __forceinline__ void fast_rebuild_col(const double *Lt, const double *Et, const double *str, int lane,
-                                                 d4 (&acc)[FastShape<K>::NT])
+__device__ __forceinline__ void fast_rebuild_col(const double *Lt, const double *str, int lane, d4 (&acc)[FastShape<K>::NT])
 {
     using F = FastShape<K>;
-    constexpr int NT = F::NT, N = F::N;
+    constexpr int NT = F::NT;
     constexpr int KEND = (4 * J + 4 + (J == 0 ? 1 : 0) < F::NKS) ? 4 * J + 4 + (J == 0 ? 1 : 0) : F::NKS;
-    const int c = lane & 15, g = lane >> 4;
-    int eoff[NT];
-#pragma unroll
-    for (int I = J; I < NT; ++I) {
-        const int rho = fast_rho<N>(16 * I + c);
-        eoff[I] = (rho >> 4) * 64 + g * 16 + (rho & 15);
-    }
 #pragma unroll
     for (int ks = 0; ks < KEND; ++ks) {
-        double fo[NT], fe[NT];
+        double fo[NT];
 #pragma unroll
         for (int I = J; I < NT; ++I) {
             const int Kc = ks >> 2;
             fo[I] = (Kc <= I) ? Lt[(I * (I + 1) / 2 + Kc) * 256 + (ks & 3) * 64 + lane] : str[lane];
-            fe[I] = Et[ks * 128 + eoff[I]];
         }
 #pragma unroll
-        for (int I = J; I < NT; ++I) {
-            acc[I - J] = __builtin_amdgcn_mfma_f64_16x16x4f64(fo[I], fo[J], acc[I - J], 0, 0, 0);
-            acc[I - J] = __builtin_amdgcn_mfma_f64_16x16x4f64(fe[I], fe[J], acc[I - J], 0, 0, 0);
-        }
+        for (int I = J; I < NT; ++I) acc[I - J] = __builtin_amdgcn_mfma_f64_16x16x4f64(fo[I], fo[J], acc[I - J], 0, 0, 0);
     }
 }
 
 // ... + p d0^T + d0 p^T (one k-step: A = [p, d0], B = [d0, p]) and out: the mirror triangle straight from the accumulators,
 // the lower triangle of the off-diagonal tiles through a private 16 x 17 transpose buffer.
+// Before either store every element takes its share of the even-part product, P+(t, s) += EE(rho(t), rho(s)) (vector rows and
+// columns read an exact zero): both orientations carry the same sum.
 template <int K, int J>
-__device__ __forceinline__ void fast_store_col(const double *pd, double *bufs, double *oP, int lane, d4 (&acc)[FastShape<K>::NT], bool lower_only)
+__device__ __forceinline__ void fast_store_col(const double *pd, const double *ee, double *bufs, double *oP, int lane,
+                                               d4 (&acc)[FastShape<K>::NT], bool lower_only)
 {
     using F = FastShape<K>;
-    constexpr int NT = F::NT, N = F::N;
+    constexpr int NT = F::NT, N = F::N, EES = FastEE<K>::EES, PAD = FastEE<K>::PAD;
     const int c = lane & 15, g = lane >> 4;
     {
         const int rj = fast_rho<N>(16 * J + c);
@@ -448,6 +504,13 @@ __device__ __forceinline__ void fast_store_col(const double *pd, double *bufs, d
             const int ri = fast_rho<N>(16 * I + c);
             const double af = pd[g == 0 ? ri : (g == 1 ? 32 + ri : 31)];
             acc[I - J] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[I - J], 0, 0, 0);
+        }
+        const double *eec = ee + (rj & PAD);                     // (31 & PAD = PAD)
+#pragma unroll
+        for (int I = J; I < NT; ++I) {
+            const unsigned rw = g == 0 ? fast_rho_pack<K>(I, 0) : (g == 1 ? fast_rho_pack<K>(I, 1) : (g == 2 ? fast_rho_pack<K>(I, 2) : fast_rho_pack<K>(I, 3)));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[I - J][r] += eec[((rw >> (8 * r)) & 0xffu) * EES];
         }
     }
     double *o = oP + c + g * N;                      // lane part of both orientations
@@ -959,19 +1022,36 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         const int rho = 16 * hr + lane;
         if (lane < 16 && rho < NROT) pd[rho] = s + (0.5 * ((double)N + 0.5)) * pd[32 + rho];
     }
+    // E^ E^^T where E^ lives: tile (0, 0) on wave 0, (1, 0) on wave 2, (1, 1) on wave 3; published over E^ once every wave
+    // has read its fragments and row sums
+    using EE = FastEE<K>;
+    static_assert(NROT <= EE::PAD && EE::wave_of(0, 0) == 0 && EE::wave_of(1, 0) == 2 && EE::wave_of(1, 1) == 3, "EE tiles");
+    d4 eacc = {0.0, 0.0, 0.0, 0.0};
+    if (wave == 0) eacc = fast_ee_tile<K, 0, 0>(Et, lane);
+    else if constexpr (EE::NTE > 1) {
+        if (wave == 2) eacc = fast_ee_tile<K, 1, 0>(Et, lane);
+        else if (wave == 3) eacc = fast_ee_tile<K, 1, 1>(Et, lane);
+    }
+    __syncthreads();                                             // E^ is dead
+    double *ee = U;
+    if (wave == 0) fast_ee_publish<K, 0, 0>(ee, lane, eacc);
+    else if constexpr (EE::NTE > 1) {
+        if (wave == 2) fast_ee_publish<K, 1, 0>(ee, lane, eacc);
+        else if (wave == 3) fast_ee_publish<K, 1, 1>(ee, lane, eacc);
+    }
     d4 acc[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
-    if (wave == 0) fast_rebuild_col<K, 0>(Lt, Et, str, lane, acc);
-    else if (wave == 1) fast_rebuild_col<K, 1>(Lt, Et, str, lane, acc);
-    else if (wave == 2) fast_rebuild_col<K, 2>(Lt, Et, str, lane, acc);
-    else if constexpr (NT > 3) fast_rebuild_col<K, 3>(Lt, Et, str, lane, acc);
-    __syncthreads();                                             // factor and E^ are dead; p is complete
+    if (wave == 0) fast_rebuild_col<K, 0>(Lt, str, lane, acc);
+    else if (wave == 1) fast_rebuild_col<K, 1>(Lt, str, lane, acc);
+    else if (wave == 2) fast_rebuild_col<K, 2>(Lt, str, lane, acc);
+    else if constexpr (NT > 3) fast_rebuild_col<K, 3>(Lt, str, lane, acc);
+    __syncthreads();                                             // the factor is dead; p and EE are complete
     SLK_FSTAMP(14);
-    if (wave == 0) fast_store_col<K, 0>(pd, Lt, oP, lane, acc, a.lower_only != 0);
-    else if (wave == 1) fast_store_col<K, 1>(pd, Lt, oP, lane, acc, a.lower_only != 0);
-    else if (wave == 2) fast_store_col<K, 2>(pd, Lt, oP, lane, acc, a.lower_only != 0);
-    else if constexpr (NT > 3) fast_store_col<K, 3>(pd, Lt, oP, lane, acc, a.lower_only != 0);
+    if (wave == 0) fast_store_col<K, 0>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
+    else if (wave == 1) fast_store_col<K, 1>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
+    else if (wave == 2) fast_store_col<K, 2>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
+    else if constexpr (NT > 3) fast_store_col<K, 3>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
     SLK_STAMP_NR(15);
     return true;
 }
