@@ -468,6 +468,25 @@ namespace localization
             sync_device();
             slk::check(slk_nees(h.get(), truth, t0, n, nees_out, err, where), "slk_nees");
         }
+
+        /** raw form of slk_ensemble_moments (include/slk.h): the moments across the filters of the handle's batch -- for
+         * this one-filter object the centre is its own mean (or its error against truth), the spread zero and mean_cov
+         * its covariance on the range; weights [B], truth [B][Nq] in the storage layout, either may be null.  The
+         * filter is not modified. */
+        void ensembleMoments(int groups, const double *weights, const double *truth, int t0, int n, double *center,
+                             double *spread, double *mean_cov, double *ess = 0, int where = SLK_HOST)
+        {
+            sync_device();
+            slk::check(slk_ensemble_moments(h.get(), groups, weights, truth, t0, n, center, spread, mean_cov, ess, where),
+                       "slk_ensemble_moments");
+        }
+        /** raw form of slk_gather_states (include/slk.h): filter b of the handle's batch becomes a copy of filter src[b] */
+        void gatherStates(const int *src, int where = SLK_HOST)
+        {
+            sync_device();
+            slk::check(slk_gather_states(h.get(), src, where), "slk_gather_states");
+            device_changed();
+        }
         /**@brief Normalised innovation squared nu^T S^-1 nu of the update that update(z, h, R) would make (all rows, before
          * any significance test), on the device (slk_nis); logdet, when given, receives log det S, so that the Gaussian
          * log-likelihood of z is -0.5 (nis + logdet + m log(2 pi)).  NaN if S is not positive definite.  h = registered

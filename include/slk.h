@@ -432,6 +432,57 @@ int slk_nis(slk_filter *f, int model, const double *params, int p_stride, const 
             const double *R, int r_stride, double *nis /*[B]*/, double *logdet /*[B] or NULL*/, int where);
 int slk_get_sigma(slk_filter *f, int t0, int n, double *sigma /*[B][n]*/, int where);
 
+/* ---- across the filters of the batch (the reference has no such call): with slk_nis the loop weight -> estimate ->
+ *      resample of a filter bank or a particle cloud stays on the device.
+ *
+ *      slk_ensemble_moments: the moments of the batch, or of `groups` = G groups of it; group g is the filters
+ *        [g B / G, (g + 1) B / G).  weights [B] (NULL = uniform), normalised per group: w~_b = w_b / sum_group w;
+ *        ess [G] = (sum w)^2 / sum w^2.  The range [t0, t0 + n) follows the rules of slk_nees (it may cut an SO(3) block).
+ *        Error mode (truth [B][Nq] given): e_b = (truth_b [-] mu_b) on the range, exactly as slk_nees takes it;
+ *          center [G][n] = ebar = sum w~_b e_b (the bias), spread = sum w~_b (e_b - ebar)(e_b - ebar)^T.
+ *        Mixture mode (truth NULL): center [G][Nq] = the weighted manifold mean of the group's means over the WHOLE state,
+ *          in the storage layout, by the pinned iteration: ref = the mean of the group's first filter; one pass is
+ *          dbar = sum w~_b (mu_b [-] ref) over all N indices, then ref <- ref [+] dbar; it stops after the pass in which
+ *          |dbar|_2 <= 1e-12, or after 100 passes.  spread = sum w~_b d_b d_b^T, d_b = (mu_b [-] center) on the range.
+ *        Both modes: mean_cov = sum w~_b P_b[range, range].  The moment-matched covariance of the mixture is
+ *          spread + mean_cov (the caller adds them); in error mode spread ~ mean_cov is the Monte-Carlo consistency
+ *          check.  Population sums: Bessel's factor is the caller's.  spread and mean_cov are [G][n * n], full n x n
+ *          column-major, both triangles written from one value (exactly symmetric).
+ *        center, spread, mean_cov and ess may each be NULL (not wanted); all four NULL is SLK_E_INVALID.
+ *        A group with a negative, NaN or infinite weight, or whose weights do not sum to something > 0 (and finite), gets
+ *        NaN in all of its outputs; the other groups are unaffected, the call returns SLK_OK and sets no status bit.
+ *        Read-only like slk_nees: mean, P, status bits and outlier counts stay bit for bit what they were.  P is read from
+ *        its LOWER triangle only and never factored: a lower-only covariance is not completed and stays lower-only, and P
+ *        need not be positive definite.  Both kinds, every N.  Device work is enqueued on the handle's stream (up to
+ *        seven launches, no host synchronisation between them); host outputs are synchronised.
+ *        Deterministic: every sum over filters runs in a fixed order (per-chunk partials in the workspace, added in
+ *        index order; no atomics), and the chunking depends on (B, G, N, n) only, so two calls on the same state give
+ *        bit-identical outputs.
+ *        Workspace (doubles, rounded up to 8, reserved before any launch and kept by the handle; a failed reservation
+ *        returns with nothing launched), with Bg = B / G, E = n (n + 1) / 2, c = Nq in mixture mode and n in error mode:
+ *          2 B + G + G c + B n + [Cc > 1] G Cc E + [Cs > 1] G Cs E,
+ *          Cs = ceil(Bg / 256) chunks of the spread, Cc = ceil(Bg / F) chunks of the mean covariance with
+ *          F = ceil(Bg / min(ceil(Bg / 8), max(1, ceil(2048 / (G ceil(E / 256))))));
+ *        a host call adds G n^2 for each of spread and mean_cov that is wanted.
+ *        SLK_E_INVALID, nothing launched: groups < 1, B % groups != 0, the range errors of slk_nees, all outputs NULL,
+ *        `where` other than SLK_HOST / SLK_DEVICE.  SLK_E_UNSUPPORTED: more than 65535 chunks in a group (16 M filters).
+ *
+ *      slk_gather_states: filter b becomes a copy of the old filter src[b] -- mean, P, status bits and outlier count --
+ *        bit for bit what slk_get_state, a host index and slk_set_state give (plus the same index on status and
+ *        outliers): resampling, hypothesis pruning, scenario fan-out.  Drawing the indices from the weights stays with
+ *        the caller (the library holds no RNG).  One launch into the handle's second buffers, reserved before it
+ *        (slk_mean_device_ptr / slk_cov_device_ptr change, as after slk_msckf_slide).  A lower-only covariance is copied
+ *        as its lower triangle (N (N + 1) / 2 doubles each way per filter) and stays lower-only; a complete one is
+ *        copied whole.  Both kinds, every N.
+ *        An index outside 0 .. B - 1: host-resident src gives SLK_E_INVALID before any launch, the handle untouched;
+ *        device-resident src makes that filter keep its own state and sets its SLK_ST_BAD_INDEX, the others unaffected.
+ *        SLK_E_INVALID also for a NULL src and for `where` other than SLK_HOST / SLK_DEVICE. ---- */
+int slk_ensemble_moments(slk_filter *f, int groups, const double *weights /*[B] or NULL*/,
+                         const double *truth /*[B][Nq] or NULL*/, int t0, int n,
+                         double *center, double *spread /*[G][n*n]*/, double *mean_cov /*[G][n*n]*/,
+                         double *ess /*[G] or NULL*/, int where);
+int slk_gather_states(slk_filter *f, const int *src /*[B]*/, int where);
+
 /* ---- arithmetic of the covariance rebuild (Msckf.hpp:665 -> :574-589): SLK_PREC_F64 (default, the
  *      parity path), SLK_PREC_F32 (fp32 MFMA) or SLK_PREC_BF16 (bf16 operands, fp32 accumulation).
  *      The reduced modes exist for the tolerance sweep of BASELINE.json config 5; the reference is

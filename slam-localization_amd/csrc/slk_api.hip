@@ -21,6 +21,7 @@
 #include "slk_ekf_model.hpp"
 #include "slk_pose.hpp"
 #include "slk_consistency.hpp"
+#include "slk_ensemble.hpp"
 #include "slk_trajectory.hpp"
 
 // The largest step-kernel instantiations are compiled in translation units of their own (slk_inst_big.hip,
@@ -66,12 +67,16 @@ struct slk_filter {
     size_t cap_mean_alt = 0, cap_P_alt = 0;             // setMeasurement) are built into it on the stream and swapped in
     int *d_status;
     unsigned *d_outliers;
+    int *d_status_alt = nullptr;                        // slk_gather_states: the status words and outlier counts move with
+    unsigned *d_outliers_alt = nullptr;                 // the filters, out of place like the state (allocated on first use)
     Stage st_u, st_Q, st_mp, st_z, st_R, st_X, st_Z, st_tmpP, st_tmpM;
     Stage ws_L, ws_DR;            // large-state workspaces (N > 80), allocated on first use
     Stage ws_ekf;                 // EKF update workspace, allocated on first use
     Stage ws_lin;                 // EKF update from a registered model: zmean, H of the linearisation and its skip flags
     Stage ws_cons;                // slk_nees / slk_sample_states workspace (consistency_ws), allocated on first use
     Stage st_truth, st_rec;       // slk_step_n (host route): the truths of all steps, the device copy of the records
+    Stage ws_ens;                 // slk_ensemble_moments workspace (ens_plan) and the staged outputs of a host call
+    Stage st_idx;                 // slk_gather_states: the indices of a host call
     Stage ws_nis;                 // slk_nis / the NIS records of slk_step_n_diag: S and nu of the emission, the outputs of a
                                   // host call, the status words the shadow launches may set (nis_ws)
     // Msckf rotation-item descriptors, one table per window length k the handle has run (a sliding window alternates
@@ -175,7 +180,7 @@ void slk_destroy(slk_filter *f)
     (void)hipSetDevice(f->cfg.device);
     (void)hipStreamSynchronize(f->stream);
     Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_X, &f->st_Z, &f->st_tmpP, &f->st_tmpM,
-                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_cons, &f->st_truth, &f->st_rec, &f->ws_nis};
+                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_cons, &f->st_truth, &f->st_rec, &f->ws_nis, &f->ws_ens, &f->st_idx};
     for (Stage *s : st) if (s->p) (void)hipFree(s->p);
     for (auto &kv : f->rtabs) if (kv.second.dev) (void)hipFree(kv.second.dev);
     if (f->d_mean) (void)hipFree(f->d_mean);
@@ -184,6 +189,8 @@ void slk_destroy(slk_filter *f)
     if (f->d_P_alt) (void)hipFree(f->d_P_alt);
     if (f->d_status) (void)hipFree(f->d_status);
     if (f->d_outliers) (void)hipFree(f->d_outliers);
+    if (f->d_status_alt) (void)hipFree(f->d_status_alt);
+    if (f->d_outliers_alt) (void)hipFree(f->d_outliers_alt);
     (void)hipEventDestroy(f->ev0);
     (void)hipEventDestroy(f->ev1);
     if (f->own_stream) (void)hipStreamDestroy(f->stream);
@@ -1689,6 +1696,151 @@ int slk_get_sigma(slk_filter *f, int t0, int n, double *sigma, int where)
         HIPCHECK(hipStreamSynchronize(f->stream));
     }
     return SLK_OK;
+}
+
+// ---- across the filters of the batch (slk_ensemble.hpp): moments of the batch or of groups of it, and the gather
+// Every argument is checked and every buffer reserved before the first launch.  The kernels read the lower triangle of
+// P only, so a lower-only covariance (upper_stale) is neither completed nor changed.
+int slk_ensemble_moments(slk_filter *f, int groups, const double *weights, const double *truth, int t0, int n,
+                         double *center, double *spread, double *mean_cov, double *ess, int where)
+{
+    if (!f || groups < 1 || f->B % groups != 0 || t0 < 0 || n < 1 || n > f->lay.N - t0) return SLK_E_INVALID;
+    if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
+    if (!center && !spread && !mean_cov && !ess) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const Lay &L = f->lay;
+    const int B = f->B, G = groups, N = L.N, Nq = L.Nq;
+    const bool mixture = truth == nullptr;
+    const EnsPlan pl = ens_plan(B, G, Nq, n, mixture);
+    const size_t nn = (size_t)n * n;
+    const bool need_centre = center || spread;                 // (the spread is taken about the centre / the bias)
+    const size_t lds = ens_centre_lds(N, Nq);
+    if (mixture && need_centre && lds > 160 * 1024) { g_err = "ensemble_moments: state too large for the centre kernel"; return SLK_E_UNSUPPORTED; }
+    if (pl.cov_chunks > 65535 || pl.spr_chunks > 65535) {            // (more than 16 M filters in one group)
+        g_err = "ensemble_moments: group too large for the reduction grids"; return SLK_E_UNSUPPORTED;
+    }
+    // a host call stages spread and mean_cov behind the plan's workspace
+    const size_t stage_out = where == SLK_HOST ? (spread ? (size_t)G * nn : 0) + (mean_cov ? (size_t)G * nn : 0) : 0;
+    int rc = stage_reserve(f, f->ws_ens, pl.total + stage_out);
+    if (rc) return rc;
+    double *ws = f->ws_ens.p;
+    const double *dt = nullptr;
+    // (the truth of a host call goes through st_u, the stage of the process inputs, as slk_nees does: every step that
+    // takes host inputs uploads its own u again, and a stage only ever grows)
+    rc = stage_in(f, f->st_u, truth, (size_t)B * Nq, where, &dt);
+    if (rc) return rc;
+#ifdef SLK_DEV_N60
+    g_err = "development build: no ensemble kernels"; return SLK_E_UNSUPPORTED;
+#else
+    if (mixture && need_centre) {
+        rc = ensure_dynamic_lds(reinterpret_cast<const void *>(ens_centre_kernel), f->cfg.device, lds);
+        if (rc) return rc;
+    }
+    const double *dw = weights;
+    if (weights && where == SLK_HOST) {
+        HIPCHECK(hipMemcpyAsync(ws + pl.w_raw, weights, (size_t)B * sizeof(double), hipMemcpyHostToDevice, f->stream));
+        dw = ws + pl.w_raw;
+    }
+    const bool dev = where == SLK_DEVICE;
+    double *wn = ws + pl.wn, *D = ws + pl.D;
+    double *dess = dev && ess ? ess : ws + pl.ess;
+    double *dcentre = dev && center ? center : ws + pl.centre;
+    double *dspread = dev ? spread : ws + pl.total;
+    double *dcov = dev ? mean_cov : ws + pl.total + (spread ? (size_t)G * nn : 0);
+    const int eb = (pl.E + 255) / 256;
+    hipLaunchKernelGGL(ens_weights_kernel, dim3(G), dim3(256), 0, f->stream, dw, pl.Bg, wn, dess);
+    HIPCHECK(hipGetLastError());
+    if (need_centre) {
+        const unsigned dgrid = (unsigned)(((size_t)B * n + 255) / 256);
+        if (mixture) {
+            hipLaunchKernelGGL(ens_centre_kernel, dim3(G), dim3(ENS_CENTRE_THREADS), lds, f->stream, L,
+                               (const double *)f->d_mean, (const double *)wn, pl.Bg, dcentre);
+            HIPCHECK(hipGetLastError());
+        }
+        if (!mixture || spread) {
+            hipLaunchKernelGGL(ens_dev_kernel, dim3(dgrid), dim3(256), 0, f->stream, L, (const double *)f->d_mean, dt,
+                               (const double *)dcentre, B, pl.Bg, t0, n, D);
+            HIPCHECK(hipGetLastError());
+        }
+        if (!mixture) {
+            hipLaunchKernelGGL(ens_bias_kernel, dim3((unsigned)((n + 15) / 16) * G), dim3(256), 0, f->stream, (const double *)D,
+                               (const double *)wn, pl.Bg, n, dcentre);
+            HIPCHECK(hipGetLastError());
+        }
+    }
+    if (spread) {
+        const int T = (n + 15) / 16, tiles = T * (T + 1) / 2;
+        hipLaunchKernelGGL(ens_spread_kernel, dim3((unsigned)tiles * G, pl.spr_chunks), dim3(256), 0, f->stream,
+                           (const double *)D, (const double *)wn, mixture ? (const double *)nullptr : (const double *)dcentre,
+                           pl.Bg, n, pl.spr_chunks, ws + pl.pspr, dspread);
+        HIPCHECK(hipGetLastError());
+    }
+    if (mean_cov) {
+        hipLaunchKernelGGL(ens_meancov_kernel, dim3((unsigned)eb * G, pl.cov_chunks), dim3(256), 0, f->stream,
+                           (const double *)f->d_P, (const double *)wn, N, t0, n, pl.Bg, pl.cov_fc, pl.cov_chunks,
+                           ws + pl.pcov, dcov);
+        HIPCHECK(hipGetLastError());
+    }
+    {   // the chunks of both reductions, added in index order by one launch
+        const double *rp[2]; int rc_[2]; double *ro[2]; int nr = 0;
+        if (spread && pl.spr_chunks > 1) { rp[nr] = ws + pl.pspr; rc_[nr] = pl.spr_chunks; ro[nr] = dspread; ++nr; }
+        if (mean_cov && pl.cov_chunks > 1) { rp[nr] = ws + pl.pcov; rc_[nr] = pl.cov_chunks; ro[nr] = dcov; ++nr; }
+        if (nr) {
+            hipLaunchKernelGGL(ens_reduce_kernel, dim3((unsigned)eb * G, nr), dim3(256), 0, f->stream, rp[0], rc_[0], ro[0],
+                               rp[nr - 1], rc_[nr - 1], ro[nr - 1], n);
+            HIPCHECK(hipGetLastError());
+        }
+    }
+    if (dev) {
+        return SLK_OK;
+    }
+    if (center) HIPCHECK(hipMemcpyAsync(center, dcentre, (size_t)G * pl.ldc * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (spread) HIPCHECK(hipMemcpyAsync(spread, dspread, (size_t)G * nn * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (mean_cov) HIPCHECK(hipMemcpyAsync(mean_cov, dcov, (size_t)G * nn * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (ess) HIPCHECK(hipMemcpyAsync(ess, dess, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHECK(hipStreamSynchronize(f->stream));
+    return SLK_OK;
+#endif
+}
+
+int slk_gather_states(slk_filter *f, const int *src, int where)
+{
+    if (!f || !src || (where != SLK_HOST && where != SLK_DEVICE)) return SLK_E_INVALID;
+    const size_t B = (size_t)f->B;
+    if (where == SLK_HOST)
+        for (size_t b = 0; b < B; ++b)
+            if (src[b] < 0 || src[b] >= f->B) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const int lower = f->upper_stale ? 1 : 0;
+    const long long chunks = (gather_elems(f->lay.N, 0) + GATHER_CHUNK - 1) / GATHER_CHUNK;
+    if (chunks > 65535) { g_err = "gather: state too large for the gather kernel's grid"; return SLK_E_UNSUPPORTED; }
+    int rc = reserve_alt(f, B * f->lay.Nq, B * (size_t)f->lay.N * f->lay.N);
+    if (rc) return rc;
+    if (!f->d_status_alt) HIPCHECK(hipMalloc(&f->d_status_alt, B * sizeof(int)));
+    if (!f->d_outliers_alt) HIPCHECK(hipMalloc(&f->d_outliers_alt, B * sizeof(unsigned)));
+    const int *ds = src;
+    if (where == SLK_HOST) {
+        rc = stage_reserve(f, f->st_idx, (B * sizeof(int) + sizeof(double) - 1) / sizeof(double));
+        if (rc) return rc;
+    }
+#ifdef SLK_DEV_N60
+    g_err = "development build: no ensemble kernels"; return SLK_E_UNSUPPORTED;
+#else
+    if (where == SLK_HOST) {
+        HIPCHECK(hipMemcpyAsync(f->st_idx.p, src, B * sizeof(int), hipMemcpyHostToDevice, f->stream));
+        ds = reinterpret_cast<const int *>(f->st_idx.p);
+    }
+    const long long nch = (gather_elems(f->lay.N, lower) + GATHER_CHUNK - 1) / GATHER_CHUNK;
+    hipLaunchKernelGGL(gather_states_kernel, dim3(f->B, (unsigned)nch), dim3(256), 0, f->stream, (const double *)f->d_mean,
+                       (const double *)f->d_P, (const int *)f->d_status, (const unsigned *)f->d_outliers, ds, f->d_mean_alt,
+                       f->d_P_alt, f->d_status_alt, f->d_outliers_alt, f->B, f->lay.N, f->lay.Nq, lower);
+    HIPCHECK(hipGetLastError());
+    swap_state_buffers(f);
+    std::swap(f->d_status, f->d_status_alt);
+    std::swap(f->d_outliers, f->d_outliers_alt);
+    if (where == SLK_HOST) HIPCHECK(hipStreamSynchronize(f->stream));   // caller may reuse its indices
+    return SLK_OK;
+#endif
 }
 
 } // extern "C"

@@ -36,6 +36,7 @@ EXPORTS = [
     "slk_sample_states", "slk_step_n", "slk_step_n_slide", "slk_msckf_slide",
     "slk_ekf_linearize", "slk_update_ekf_model", "slk_step_ekf", "slk_step_n_ekf",
     "slk_nis", "slk_get_sigma", "slk_step_n_diag",
+    "slk_ensemble_moments", "slk_gather_states",
 ]
 
 
@@ -132,6 +133,8 @@ def load_library(path=None):
     lib.slk_nis.argtypes = [vp, ip, vp, ip, vp, vp, ip, vp, ip, vp, vp, ip]
     lib.slk_get_sigma.argtypes = [vp, ip, ip, vp, ip]
     lib.slk_step_n_diag.argtypes = [vp, C.POINTER(Traj), vp, ip, C.POINTER(TrajDiag), ip]
+    lib.slk_ensemble_moments.argtypes = [vp, ip, vp, vp, ip, ip, vp, vp, vp, vp, ip]
+    lib.slk_gather_states.argtypes = [vp, vp, ip]
     if path is None:
         _lib = lib
     return lib
@@ -616,6 +619,91 @@ class _FilterBatch:
         out = np.empty((self.B, max(n, 0)))
         _check(self._lib.slk_get_sigma(self._h, int(t0), n, out.ctypes.data, HOST), "slk_get_sigma")
         return out
+
+    def ensemble_moments(self, weights=None, truth=None, t0=0, n=None, groups=1, ess=False, device=None):
+        """Moments across the filters of the batch, or of `groups` = G equal groups of consecutive filters, on the tangent
+        indices [t0, t0 + n) (default: to N).  weights [B] (None = uniform) are normalised per group.  Returns a dict:
+          truth given (error mode):  "center" [G, n] = the weighted mean of e_b = (truth_b [-] mu_b) (the bias), "spread"
+                                     [G, n, n] = the weighted covariance of e_b about it;
+          truth None (mixture mode): "center" [G, Nq] = the weighted manifold mean of the means (whole state, storage
+                                     layout), "spread" [G, n, n] = sum w_b d_b d_b^T, d_b = (mu_b [-] center) on the range;
+          both: "mean_cov" [G, n, n] = sum w_b P_b[range, range]; ess=True adds "ess" [G] = (sum w)^2 / sum w^2.
+        The moment-matched covariance of the mixture is spread + mean_cov; population sums (no Bessel factor).  A group
+        with a negative or non-finite weight or a weight sum that is not > 0 gets NaN outputs.  The filters are not
+        modified and P is not downloaded.  numpy in -> numpy out; torch device tensors in (weights and / or truth,
+        contiguous float64) -> torch device tensors out (torch's stream is synchronised before the call, the handle's
+        after it).  device = a torch device asks for device tensors out when there is no input to tell by (uniform
+        weights, mixture mode)."""
+        B, Nq, G = self.B, self.Nq, int(groups)
+        n = self.N - int(t0) if n is None else int(n)
+        devs = [a for a in (weights, truth) if a is not None and _is_dev(a)]
+        if devs and len(devs) != sum(a is not None for a in (weights, truth)):
+            raise SlkError("all arguments of one call must live on the same side (host or device)")
+        where = DEVICE if devs or (device is not None and weights is None and truth is None) else HOST
+        keep = []
+
+        def arg(a, count, name):
+            if a is None:
+                return None
+            if _is_dev(a):
+                if not a.is_contiguous() or a.numel() != count or str(a.dtype) != "torch.float64" or not a.is_cuda:
+                    raise SlkError(f"ensemble_moments: {name} must be a contiguous float64 device tensor of {count} values")
+                keep.append(a)
+                return a.data_ptr()
+            a = np.asarray(a, dtype=np.float64)
+            if name == "truth":
+                if a.shape[-1] != Nq or a.ndim > 2 or (a.ndim == 2 and a.shape[0] not in (1, B)):
+                    raise SlkError(f"ensemble_moments: truth must be [{B}, {Nq}], got {a.shape}")
+                a = np.broadcast_to(a.reshape(-1, Nq), (B, Nq))
+            elif a.size != count:
+                raise SlkError(f"ensemble_moments: {name} must hold {count} values, got {a.shape}")
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+            return a.ctypes.data
+
+        wp, tp = arg(weights, B, "weights"), arg(truth, B * Nq, "truth")
+        Ge, ne = max(G, 0), max(n, 0)
+        nc = ne if truth is not None else Nq
+        if where == DEVICE:
+            import torch
+            dev = devs[0].device if devs else torch.device(device)
+            torch.cuda.current_stream(dev).synchronize()      # (the handle's stream does not wait for torch's)
+            mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+            ptr = lambda a: a.data_ptr()
+        else:
+            mk = lambda *shape: np.empty(shape)
+            ptr = lambda a: a.ctypes.data
+        out = {"center": mk(Ge, nc), "spread": mk(Ge, ne, ne), "mean_cov": mk(Ge, ne, ne)}
+        if ess:
+            out["ess"] = mk(Ge)
+        _check(self._lib.slk_ensemble_moments(self._h, G, wp, tp, int(t0), n, ptr(out["center"]), ptr(out["spread"]),
+                                              ptr(out["mean_cov"]), ptr(out["ess"]) if ess else None, where),
+               "slk_ensemble_moments")
+        if where == DEVICE:
+            self.sync()                                        # torch may read the outputs on any stream
+        return out                                             # (spread and mean_cov are symmetric: row- or column-major)
+
+    def gather(self, src):
+        """Filter b becomes a copy of the old filter src[b] (mean, P, status bits, outlier count): resampling, pruning,
+        fan-out, in one launch on the device.  src [B] integers: numpy (an index outside 0 .. B - 1 raises, nothing
+        changed) or a torch int32 device tensor (such a filter keeps its state and gets ST_BAD_INDEX).  device_pointers()
+        change."""
+        if _is_dev(src):
+            if not src.is_contiguous() or src.numel() != self.B or str(src.dtype) != "torch.int32" or not src.is_cuda:
+                raise SlkError(f"gather: src must be a contiguous int32 device tensor of {self.B} indices")
+            import torch
+            torch.cuda.current_stream(src.device).synchronize()
+            _check(self._lib.slk_gather_states(self._h, src.data_ptr(), DEVICE), "slk_gather_states")
+            self.sync()                                        # (src may be released after the call)
+            return
+        src = np.asarray(src)
+        if src.size != self.B or not np.issubdtype(src.dtype, np.integer):
+            raise SlkError(f"gather: src must be {self.B} integers, got {src.dtype} {src.shape}")
+        big = np.ascontiguousarray(src.reshape(-1), dtype=np.int64)
+        if big.size and (big.min() < -2 ** 31 or big.max() >= 2 ** 31):
+            raise SlkError("gather: index outside 0 .. B - 1")
+        idx = np.ascontiguousarray(big, dtype=np.int32)
+        _check(self._lib.slk_gather_states(self._h, idx.ctypes.data, HOST), "slk_gather_states")
 
     def sample_states(self, noise):
         """Gaussian draws from every filter's own (mu, P): out [B, S, Nq] = mu [+] (L n) for noise [B, S, N] (e.g. standard
