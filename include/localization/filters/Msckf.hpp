@@ -8,6 +8,7 @@
  *                                                                 slk_update_innovation + slk_update_selected
  *   EKF update(z, h, H, R) :284-290, update(z, h, H, R, mt) :297-349 -> slk_update_ekf
  *   ... with h = slk::FeatureProjectionModel                          -> slk_update_ekf_model (slk_ekf_linearize for a custom mt)
+ *   updateTracks(slk::FeatureTracks, sigma[, chi2])                   -> slk_update_tracks (landmarks of unknown position)
  *   muSingleState / setPkSingleState / getPkSingleState / muState (const and non-const) / getPk / setPk :351-395
  *   checkSigmaPoints :819-839 -> slk_check_sigma_points;  accept_mahalanobis_distance :844-905
  *
@@ -106,6 +107,23 @@ namespace localization
             slk::check(slk_get_outliers(h.get(), &last_outliers, SLK_HOST), "slk_get_outliers");
             device_changed();
             return last_outliers;
+        }
+
+        std::vector<double> track_points;
+        std::vector<int> run_tracks(const slk::FeatureTracks &tracks, double sigma, const double *chi2)
+        {
+            sync_device();
+            const int J = tracks.size(), N = h.N();
+            int m = J * (2 * tracks.M - 3);
+            if (m < N) m = N;
+            m += m & 1;
+            track_points.assign((std::size_t)4 * J, 0.0);
+            slk::check(slk_update_tracks(h.get(), tracks.slots.data(), 0, J, tracks.M, &sigma, 0, chi2, m, track_points.data(),
+                                         SLK_HOST), "slk_update_tracks");
+            finish_update();
+            std::vector<int> flags(J);
+            for (int j = 0; j < J; ++j) flags[j] = (int)track_points[4 * j + 3];
+            return flags;
         }
 
         /** registered models -> (id, parameter pointer) for the C ABI; anything else is a host functor */
@@ -386,6 +404,20 @@ namespace localization
             Linearised<_Measurement> lin = {mean_z};
             return update(z, lin, H, R, mt);
         }
+
+        /**@brief Multi-state-constraint update from feature tracks (slk_update_tracks; the reference has no such call):
+         * every track is triangulated from the window's poses and marginalised onto the left null space of its landmark
+         * Jacobian on the device, then the EKF update runs on the stacked rows.  sigma: the image-noise standard
+         * deviation; chi2 (optional): the caller's chi-square thresholds indexed by 2 n_obs - 3, 2M - 2 of them.
+         * Returns one flag per track: 1 used, 0 unused (fewer than two observations), -1 failed, -2 gated out;
+         * trackPoints() holds the triangulated points (x, y, z, flag per track) of the last call. */
+        std::vector<int> updateTracks(const slk::FeatureTracks &tracks, double sigma) { return run_tracks(tracks, sigma, 0); }
+        std::vector<int> updateTracks(const slk::FeatureTracks &tracks, double sigma, const std::vector<double> &chi2)
+        {
+            if ((int)chi2.size() < 2 * tracks.M - 2) throw std::invalid_argument("Msckf::updateTracks: chi2 needs 2M - 2 entries");
+            return run_tracks(tracks, sigma, chi2.data());
+        }
+        const std::vector<double> &trackPoints() const { return track_points; }
 
         void muSingleState(const _SingleState &state)            // Msckf.hpp:351-354
         {

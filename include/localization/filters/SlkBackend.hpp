@@ -79,6 +79,24 @@ namespace slk
         std::vector<double> params;   /* (x, y, z, pose index) per feature */
         void add(double x, double y, double z, int pose) { params.push_back(x); params.push_back(y); params.push_back(z); params.push_back(pose); }
     };
+    struct FeatureTracks  /* tracks of landmarks of unknown position: M observation slots { pose index, u, v } each */
+    {
+        int M;
+        std::vector<double> slots;    /* [J][M][3]; pose index -1 = empty slot */
+        explicit FeatureTracks(int slots_per_track) : M(slots_per_track) {}
+        int size() const { return (int)(slots.size() / (3 * (std::size_t)M)); }
+        int add()                     /* a new track, every slot empty; returns its index */
+        {
+            for (int s = 0; s < M; ++s) { slots.push_back(-1.0); slots.push_back(0.0); slots.push_back(0.0); }
+            return size() - 1;
+        }
+        void observe(int track, int slot, int pose, double u, double v)
+        {
+            if (track < 0 || track >= size() || slot < 0 || slot >= M) throw std::invalid_argument("FeatureTracks::observe: track or slot out of range");
+            double *p = &slots[3 * ((std::size_t)track * M + slot)];
+            p[0] = pose; p[1] = u; p[2] = v;
+        }
+    };
     struct PosePositionModel { double pose; explicit PosePositionModel(int p) : pose(p) {} };
 
     template <class T> struct is_registered_process { enum { value = 0 }; };

@@ -258,6 +258,56 @@ int slk_step_ekf(slk_filter *f, int pmodel, const double *u, int u_stride, const
                  int mmodel, const double *params, int p_stride, const double *z, int m,
                  const double *R, int r_stride, int gate, int where);
 
+/* ---- Msckf feature-track update: landmarks of UNKNOWN position (the reference has no such call: its h(mu_state, H) is a
+ *      host functor).  A track is one landmark seen from several poses of the window; it is triangulated from the
+ *      resident poses and removed from the measurement by projecting onto the left null space of its own Jacobian, all on
+ *      the device.  Msckf only.
+ *      tracks [B][t_stride] (t_stride 0 = one set shared by every filter, otherwise >= 3 J M): J tracks of M observation
+ *      slots { pose index c, u, v }; c as in SLK_MM_FEATURE_PROJ (0 = current state, c >= 1 = clone c - 1), c = -1 an
+ *      empty slot; (u, v) the normalised image point.  sigma: the image-noise standard deviation, s_stride 0 = one
+ *      shared value, 1 = [B].  2 <= M <= 32, J >= 1; m, the row count handed to the EKF update, obeys the rules of
+ *      slk_update_ekf (N <= m <= 512, m even) and m >= J (2M - 3).
+ *      Per track, at the resident mean:
+ *        1. the slots with c >= 0, pose (p_i, q_i); fewer than two: UNUSED (flag 0); two slots naming one pose: FAILED
+ *           (flag -1)
+ *        2. d_i = R(q_i) (u_i, v_i, 1)^T normalised, A = sum (I - d_i d_i^T), b = sum (I - d_i d_i^T) p_i, X = A^-1 b by a
+ *           3 x 3 Cholesky; a non-positive or NaN pivot: flag -1
+ *        3. exactly five Gauss-Newton iterations X <- X - (sum F_i^T F_i)^-1 sum F_i^T e_i on e_i = pi(l_i) - (u_i, v_i),
+ *           l_i = R(q_i)^T (X - p_i), F_i = J_i R(q_i)^T, J_i the projection Jacobian above; no early exit.  A
+ *           non-positive or NaN pivot, a non-finite X, or a depth l_i.z <= 0 at the final X: flag -1
+ *        4. at the final X: r_i = (u_i, v_i) - pi(l_i), H_x,i = the 2 x 6 block of SLK_MM_FEATURE_PROJ with Lw = X at the
+ *           pose's tangent offset, H_f,i = F_i; empty slots are zero rows
+ *        5. three Householder reflections on the 2M x 3 matrix H_f (Eigen's reflector convention, as slk_update_ekf's
+ *           reduceDimension) applied to [H_x | r]; the first three rows are dropped, the other 2M - 3 divided by sigma:
+ *           rows j (2M - 3) .. (j + 1)(2M - 3) - 1 of r and H, whitened (measurement noise I)
+ *        6. chi2 != NULL: chi2 [2M - 2], resident as `where` says, indexed by dof = 2 n_obs - 3;
+ *           gamma = r_j^T (H_j P H_j^T + I)^-1 r_j on the track's rows, P read from its lower triangle only; the track is
+ *           kept iff gamma < chi2[dof], otherwise its flag is -2.  The library holds no table: the level is the caller's.
+ *      Outputs: r [B][m], H [B][m*N] (m x N column-major, the layout slk_update_ekf takes); rows of a track whose flag is
+ *      not 1, rows >= J (2M - 3) and every column outside a row's observed poses are exact +0.0.  feat [B][J][4] (may be
+ *      NULL) = { X, flag }, flag 1 = used; X is +0.0 for flag 0 and NaN for flag -1.  Every entry of r, H and feat is
+ *      written by the launch itself.  Mean, P, status and outlier counts are not modified; a lower-only P stays so.
+ *      Pose indices outside -1 .. k (or NaN): host-resident tracks are SLK_E_INVALID before any launch; device-resident
+ *      ones give that filter SLK_ST_BAD_INDEX, its r / H are filled with NaN (its feat with NaN points and flags 0) and in
+ *      slk_update_tracks / slk_step_tracks it is skipped.  Every other bad argument (a Usckf handle, M, J, m, a stride, a
+ *      NULL tracks / sigma / r / H, `where`, a host-resident sigma <= 0) is SLK_E_INVALID, nothing launched.
+ *      slk_update_tracks: the linearisation into a workspace of the handle, then slk_update_ekf's kernel of that shape,
+ *        unchanged, with z = r, zmean = 0, R = I_m shared and gate = 0: mean, P and status are bit-identical to
+ *        slk_track_linearize(SLK_DEVICE) followed by slk_update_ekf(SLK_DEVICE) on those buffers -- except that a filter
+ *        without a used track (or with a bad pose index) is skipped and stays bit for bit what it was, its outlier count
+ *        included; every other filter's outlier count reads 0.  Rejected tracks are reported through feat.
+ *      slk_step_tracks: slk_predict followed by slk_update_tracks, bit-identical.
+ *      Workspace: B (m N + 2 m) + m^2 doubles plus one int per filter, next to slk_update_ekf's own, and B J 4 doubles
+ *      for feat on the host route; all reserved before the first launch. ---- */
+int slk_track_linearize(slk_filter *f, const double *tracks, int t_stride, int J, int M,
+                        const double *sigma, int s_stride, const double *chi2, int m,
+                        double *r, double *H, double *feat, int where);
+int slk_update_tracks(slk_filter *f, const double *tracks, int t_stride, int J, int M,
+                      const double *sigma, int s_stride, const double *chi2, int m, double *feat, int where);
+int slk_step_tracks(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,
+                    const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                    const double *chi2, int m, double *feat, int where);
+
 /* ---- fused predict + update, one kernel launch, state stays on chip between the two
  *      (the benchmark's "filter step") ---- */
 int slk_step(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,

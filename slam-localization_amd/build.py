@@ -11,7 +11,7 @@ SRC = os.path.join(HERE, "csrc", "slk_api.hip")
 UNITS = [os.path.join(HERE, "csrc", f) for f in ("slk_api.hip", "slk_inst_big.hip", "slk_inst_mid.hip", "slk_consistency.hip",
                                                 "slk_trajectory.hip", "slk_ensemble.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("slk_api.hip", "slk_inst_big.hip", "slk_inst_mid.hip", "slk_kernels.hpp", "slk_usckf.hpp",
-                                                "slk_math.hpp", "slk_step_fast.hpp", "slk_usckf_fast.hpp", "slk_general.hpp", "slk_usckf_general.hpp", "slk_usckf_wide.hpp", "slk_ekf.hpp", "slk_ekf_tiles.hpp", "slk_ekf_model.hpp", "slk_pose.hpp",
+                                                "slk_math.hpp", "slk_step_fast.hpp", "slk_usckf_fast.hpp", "slk_general.hpp", "slk_usckf_general.hpp", "slk_usckf_wide.hpp", "slk_ekf.hpp", "slk_ekf_tiles.hpp", "slk_ekf_model.hpp", "slk_tracks.hpp", "slk_pose.hpp",
                                                 "slk_consistency.hpp", "slk_consistency.hip", "slk_trajectory.hpp", "slk_trajectory.hip",
                                                 "slk_ensemble.hpp", "slk_ensemble.hip")]
 DEPS.append(os.path.join(os.path.dirname(HERE), "include", "slk.h"))

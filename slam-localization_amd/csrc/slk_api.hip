@@ -19,6 +19,7 @@
 #include "slk_ekf.hpp"
 #include "slk_ekf_tiles.hpp"
 #include "slk_ekf_model.hpp"
+#include "slk_tracks.hpp"
 #include "slk_pose.hpp"
 #include "slk_consistency.hpp"
 #include "slk_ensemble.hpp"
@@ -73,6 +74,7 @@ struct slk_filter {
     Stage ws_L, ws_DR;            // large-state workspaces (N > 80), allocated on first use
     Stage ws_ekf;                 // EKF update workspace, allocated on first use
     Stage ws_lin;                 // EKF update from a registered model: zmean, H of the linearisation and its skip flags
+    Stage ws_trk;                 // feature-track update: r, zmean = 0, H, R = I and the skip flags (trk_ws_doubles)
     Stage ws_cons;                // slk_nees / slk_sample_states workspace (consistency_ws), allocated on first use
     Stage st_truth, st_rec;       // slk_step_n (host route): the truths of all steps, the device copy of the records
     Stage ws_ens;                 // slk_ensemble_moments workspace (ens_plan) and the staged outputs of a host call
@@ -180,7 +182,7 @@ void slk_destroy(slk_filter *f)
     (void)hipSetDevice(f->cfg.device);
     (void)hipStreamSynchronize(f->stream);
     Stage *st[] = {&f->st_u, &f->st_Q, &f->st_mp, &f->st_z, &f->st_R, &f->st_X, &f->st_Z, &f->st_tmpP, &f->st_tmpM,
-                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_cons, &f->st_truth, &f->st_rec, &f->ws_nis, &f->ws_ens, &f->st_idx};
+                   &f->ws_L, &f->ws_DR, &f->ws_ekf, &f->ws_lin, &f->ws_trk, &f->ws_cons, &f->st_truth, &f->st_rec, &f->ws_nis, &f->ws_ens, &f->st_idx};
     for (Stage *s : st) if (s->p) (void)hipFree(s->p);
     for (auto &kv : f->rtabs) if (kv.second.dev) (void)hipFree(kv.second.dev);
     if (f->d_mean) (void)hipFree(f->d_mean);
@@ -1106,6 +1108,195 @@ int slk_step_ekf(slk_filter *f, int pmodel, const double *u, int u_stride, const
     rc = launch(f, a);                                            // the predict-only call of slk_predict
     if (rc) return rc;
     return launch_ekf_model(f, dmp, p_stride, dz, m, dR, r_stride, gate);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------- Msckf feature-track update
+// The workspace of slk_update_tracks / of a host-route slk_track_linearize: r [B][m], zmean = 0 [B][m], H [B][m*N],
+// R = I [m*m], then one skip flag (int) per filter.  The two constants are written by every slk_update_tracks.
+static size_t trk_ws_doubles(const slk_filter *f, int m)
+{
+    const size_t B = (size_t)f->B;
+    const size_t n = B * ((size_t)m * f->lay.N + 2 * (size_t)m) + (size_t)m * m + (B * sizeof(int) + sizeof(double) - 1) / sizeof(double);
+    return (n + 7) / 8 * 8;
+}
+static double *trk_r(slk_filter *f) { return f->ws_trk.p; }
+static double *trk_zero(slk_filter *f, int m) { return f->ws_trk.p + (size_t)f->B * m; }
+static double *trk_H(slk_filter *f, int m) { return f->ws_trk.p + 2 * (size_t)f->B * m; }
+static double *trk_I(slk_filter *f, int m) { return trk_H(f, m) + (size_t)f->B * m * f->lay.N; }
+static int *trk_skip(slk_filter *f, int m) { return reinterpret_cast<int *>(trk_I(f, m) + (size_t)m * m); }
+
+// waves per workgroup and dynamic LDS of the track kernel: as many waves as 64 KB hold, four at the most
+static int track_waves(const slk_filter *f, int J, int M, bool gate, size_t *lds)
+{
+    const size_t per = track_wave_doubles(M, f->lay.k, gate) * sizeof(double);
+    int W = J < TRACK_MAX_WAVES ? J : TRACK_MAX_WAVES;
+    while (W > 1 && W * per > 65536) --W;
+    *lds = W * per;
+    return W;
+}
+
+// Msckf, the shape rules and the row rules of slk_update_ekf; host-resident arguments: sigma and the pose indices too
+static int check_tracks(slk_filter *f, const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                        int m, int where)
+{
+    if (!f || f->lay.kind != SLK_MSCKF || !tracks || !sigma) return SLK_E_INVALID;
+    if (where != SLK_HOST && where != SLK_DEVICE) return SLK_E_INVALID;
+    if (M < 2 || M > TRACK_MAX_M || J < 1) return SLK_E_INVALID;
+    if (m < f->lay.N || m > 512 || (m & 1)) return SLK_E_INVALID;
+    if ((long long)J * (2 * M - 3) > m) return SLK_E_INVALID;
+    if (t_stride != 0 && t_stride < 3 * J * M) return SLK_E_INVALID;
+    if (s_stride != 0 && s_stride != 1) return SLK_E_INVALID;
+    if (where == SLK_HOST) {
+        for (int b = 0; b < (s_stride ? f->B : 1); ++b)
+            if (!(sigma[b] > 0.0)) { g_err = "sigma of a track update not positive"; return SLK_E_INVALID; }
+        for (int b = 0; b < (t_stride ? f->B : 1); ++b) {
+            const double *row = tracks + (size_t)b * t_stride;
+            for (int q = 0; q < J * M; ++q)
+                if (!(row[3 * q] >= -1.0 && row[3 * q] <= (double)f->lay.k)) { g_err = "pose index of a track out of range"; return SLK_E_INVALID; }
+        }
+    }
+    return SLK_OK;
+}
+
+// what the track kernel of this shape needs ahead of its launch
+static int reserve_tracks(slk_filter *f, int J, int M, bool gate)
+{
+    size_t lds;
+    (void)track_waves(f, J, M, gate, &lds);
+    return ensure_dynamic_lds(reinterpret_cast<const void *>(msckf_track_linearize_kernel), f->cfg.device, lds);
+}
+
+// the inputs of a track call as device pointers (host route: staged copies)
+static int stage_tracks(slk_filter *f, const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                        const double *chi2, int where, const double **dtr, const double **dsg, const double **dchi)
+{
+    const size_t B = (size_t)f->B;
+    int rc = stage_in(f, f->st_mp, tracks, t_stride ? B * t_stride : (size_t)3 * J * M, where, dtr);
+    if (rc) return rc;
+    rc = stage_in(f, f->st_z, sigma, s_stride ? B : (size_t)1, where, dsg);
+    if (rc) return rc;
+    return stage_in(f, f->st_R, chi2, (size_t)2 * M - 2, where, dchi);
+}
+
+static int launch_tracks(slk_filter *f, const double *dtr, int t_stride, int J, int M, const double *dsg, int s_stride,
+                         const double *dchi, int m, double *r, double *H, double *feat, int *skip)
+{
+    TrackArgs a;
+    size_t lds;
+    a.B = f->B; a.N = f->lay.N; a.Nq = f->lay.Nq; a.k = f->lay.k; a.m = m; a.J = J; a.M = M;
+    a.W = track_waves(f, J, M, dchi != nullptr, &lds);
+    a.mean = f->d_mean; a.P = f->d_P; a.tracks = dtr; a.t_stride = t_stride; a.sigma = dsg; a.s_stride = s_stride; a.chi2 = dchi;
+    a.r = r; a.H = H; a.feat = feat; a.status = f->d_status; a.skip = skip;
+    hipLaunchKernelGGL(msckf_track_linearize_kernel, dim3(f->B), dim3(64 * a.W), lds, f->stream, a);
+    HIPCHECK(hipGetLastError());
+    return SLK_OK;
+}
+
+// every reservation of one track update at m rows; feat_n: doubles of the staged flags of a host call
+static int reserve_update_tracks(slk_filter *f, int J, int M, bool gate, int m, size_t feat_n)
+{
+    int rc = reserve_tracks(f, J, M, gate);
+    if (rc) return rc;
+    rc = stage_reserve(f, f->ws_trk, trk_ws_doubles(f, m));
+    if (rc) return rc;
+    if (feat_n) { rc = stage_reserve(f, f->st_Z, feat_n); if (rc) return rc; }
+    return reserve_ekf(f, m);
+}
+
+// the track kernel into the handle's workspace, then the EKF kernel of this shape on it with z = r, zmean = 0, R = I
+// and gate = 0: device pointers, checks and reservations (reserve_update_tracks) made by the caller.
+static int launch_update_tracks(slk_filter *f, const double *dtr, int t_stride, int J, int M, const double *dsg, int s_stride,
+                                const double *dchi, int m, double *dfeat)
+{
+    int rc = mirror_upper(f);
+    if (rc) return rc;
+    // zmean = 0 and R = I are written on every call: the workspace is shared with the host route of slk_track_linearize
+    // and laid out by m and N, so nothing in it outlives a call
+    HIPCHECK(hipMemsetAsync(trk_zero(f, m), 0, (size_t)f->B * m * sizeof(double), f->stream));
+    hipLaunchKernelGGL(track_identity_kernel, dim3((m * m + 255) / 256), dim3(256), 0, f->stream, trk_I(f, m), m);
+    HIPCHECK(hipGetLastError());
+    rc = launch_tracks(f, dtr, t_stride, J, M, dsg, s_stride, dchi, m, trk_r(f), trk_H(f, m), dfeat, trk_skip(f, m));
+    if (rc) return rc;
+    EkfArgs a;
+    ekf_base_args(f, a, m, 0, 0);
+    a.z = trk_r(f); a.zmean = trk_zero(f, m); a.H = trk_H(f, m); a.R = trk_I(f, m); a.skip = trk_skip(f, m);
+    return launch_ekf(f, a);
+}
+
+// slk_update_tracks, and with predict != 0 slk_step_tracks: every check, every
+// reservation, the staged inputs, then slk_predict's launch (if asked for), the track kernel and the EKF kernel
+static int run_update_tracks(slk_filter *f, int predict, const double *u, int u_stride, const double *Q, int q_stride,
+                             const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                             const double *chi2, int m, double *feat, int where, int pmodel = 0)
+{
+    int rc = check_tracks(f, tracks, t_stride, J, M, sigma, s_stride, m, where);
+    if (rc) return rc;
+    if (predict) { rc = check_predict(pmodel, u, u_stride, Q, q_stride); if (rc) return rc; }
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t nfeat = (size_t)f->B * J * 4;
+    const bool stage_feat = feat && where == SLK_HOST;
+    rc = reserve_update_tracks(f, J, M, chi2 != nullptr, m, stage_feat ? nfeat : 0);
+    if (rc) return rc;
+    KArgs a;
+    if (predict) {
+        base_args(f, a);
+        rc = fill_predict(f, a, pmodel, u, u_stride, Q, q_stride, where);
+        if (rc) return rc;
+    }
+    const double *dtr, *dsg, *dchi;
+    rc = stage_tracks(f, tracks, t_stride, J, M, sigma, s_stride, chi2, where, &dtr, &dsg, &dchi);
+    if (rc) return rc;
+    if (predict) { rc = launch(f, a); if (rc) return rc; }        // the predict-only call of slk_predict
+    rc = launch_update_tracks(f, dtr, t_stride, J, M, dsg, s_stride, dchi, m, stage_feat ? f->st_Z.p : feat);
+    if (rc || !stage_feat) return rc;
+    HIPCHECK(hipMemcpyAsync(feat, f->st_Z.p, nfeat * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHECK(hipStreamSynchronize(f->stream));
+    return SLK_OK;
+}
+
+extern "C" {
+
+int slk_track_linearize(slk_filter *f, const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                        const double *chi2, int m, double *r, double *H, double *feat, int where)
+{
+    int rc = check_tracks(f, tracks, t_stride, J, M, sigma, s_stride, m, where);
+    if (rc) return rc;
+    if (!r || !H) return SLK_E_INVALID;
+    HIPCHECK(hipSetDevice(f->cfg.device));
+    const size_t B = (size_t)f->B, N = (size_t)f->lay.N;
+    rc = reserve_tracks(f, J, M, chi2 != nullptr);
+    if (rc) return rc;
+    if (where == SLK_HOST) {
+        rc = stage_reserve(f, f->ws_trk, trk_ws_doubles(f, m));
+        if (rc) return rc;
+        if (feat) { rc = stage_reserve(f, f->st_Z, B * J * 4); if (rc) return rc; }
+    }
+    const double *dtr, *dsg, *dchi;
+    rc = stage_tracks(f, tracks, t_stride, J, M, sigma, s_stride, chi2, where, &dtr, &dsg, &dchi);
+    if (rc) return rc;
+    if (where == SLK_DEVICE) return launch_tracks(f, dtr, t_stride, J, M, dsg, s_stride, dchi, m, r, H, feat, nullptr);
+    rc = launch_tracks(f, dtr, t_stride, J, M, dsg, s_stride, dchi, m, trk_r(f), trk_H(f, m), feat ? f->st_Z.p : nullptr, nullptr);
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(r, trk_r(f), B * m * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHECK(hipMemcpyAsync(H, trk_H(f, m), B * m * N * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (feat) HIPCHECK(hipMemcpyAsync(feat, f->st_Z.p, B * J * 4 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHECK(hipStreamSynchronize(f->stream));
+    return SLK_OK;
+}
+
+int slk_update_tracks(slk_filter *f, const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                      const double *chi2, int m, double *feat, int where)
+{
+    return run_update_tracks(f, 0, nullptr, 0, nullptr, 0, tracks, t_stride, J, M, sigma, s_stride, chi2, m, feat, where);
+}
+
+int slk_step_tracks(slk_filter *f, int pmodel, const double *u, int u_stride, const double *Q, int q_stride,
+                    const double *tracks, int t_stride, int J, int M, const double *sigma, int s_stride,
+                    const double *chi2, int m, double *feat, int where)
+{
+    return run_update_tracks(f, 1, u, u_stride, Q, q_stride, tracks, t_stride, J, M, sigma, s_stride, chi2, m, feat, where, pmodel);
 }
 
 int slk_update_ekf(slk_filter *f, const double *z, const double *zmean, const double *H, int m,

@@ -37,6 +37,7 @@ EXPORTS = [
     "slk_ekf_linearize", "slk_update_ekf_model", "slk_step_ekf", "slk_step_n_ekf",
     "slk_nis", "slk_get_sigma", "slk_step_n_diag",
     "slk_ensemble_moments", "slk_gather_states",
+    "slk_track_linearize", "slk_update_tracks", "slk_step_tracks",
 ]
 
 
@@ -135,6 +136,9 @@ def load_library(path=None):
     lib.slk_step_n_diag.argtypes = [vp, C.POINTER(Traj), vp, ip, C.POINTER(TrajDiag), ip]
     lib.slk_ensemble_moments.argtypes = [vp, ip, vp, vp, ip, ip, vp, vp, vp, vp, ip]
     lib.slk_gather_states.argtypes = [vp, vp, ip]
+    lib.slk_track_linearize.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp, ip, vp, vp, vp, ip]
+    lib.slk_update_tracks.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp, ip, vp, ip]
+    lib.slk_step_tracks.argtypes = [vp, ip, vp, ip, vp, ip, vp, ip, ip, ip, vp, ip, vp, ip, vp, ip]
     if path is None:
         _lib = lib
     return lib
@@ -850,6 +854,112 @@ class Msckf(_FilterBatch):
             torch.cuda.current_stream(z.device).synchronize()  # (the handle's stream does not wait for torch's)
         _check(self._lib.slk_step_ekf(self._h, pmodel, ua.ptr, ua.stride, qa.ptr, qa.stride, mmodel, pa.ptr, pa.stride,
                                       za.ptr, m, ra.ptr, ra.stride, int(bool(gate)), where), "slk_step_ekf")
+
+    def _track_args(self, tracks, sigma, chi2, what):
+        """tracks [B, J, M, 3] or shared [J, M, 3] of { pose index, u, v }; sigma a number, a one-element array or [B];
+        chi2 None or [2M - 2].  numpy -> host, torch device tensors -> device (a Python number for sigma goes where
+        the tracks are)."""
+        if tracks is None or sigma is None:
+            raise SlkError(f"{what}: tracks and sigma are needed")
+        shape = tuple(tracks.shape)
+        if len(shape) not in (3, 4) or shape[-1] != 3 or (len(shape) == 4 and shape[0] != self.B):
+            raise SlkError(f"{what}: tracks must be [{self.B}, J, M, 3] or [J, M, 3], got {shape}")
+        J, M = int(shape[-3]), int(shape[-2])
+        if _is_dev(tracks):
+            import torch
+            if not tracks.is_contiguous() or str(tracks.dtype) != "torch.float64":
+                raise SlkError(f"{what}: tracks must be a contiguous float64 tensor")
+            ta = _Arg(tracks.data_ptr(), 3 * J * M if len(shape) == 4 else 0, DEVICE if tracks.is_cuda else HOST, tracks)
+            if not _is_dev(sigma):
+                sigma = torch.as_tensor(np.atleast_1d(np.asarray(sigma, dtype=np.float64)), device=tracks.device)
+            if chi2 is not None and not _is_dev(chi2):
+                chi2 = torch.as_tensor(np.ascontiguousarray(chi2, dtype=np.float64), device=tracks.device)
+        else:
+            t = np.ascontiguousarray(tracks, dtype=np.float64)
+            ta = _Arg(t.ctypes.data, 3 * J * M if len(shape) == 4 else 0, HOST, t)
+        if _is_dev(sigma):
+            if sigma.numel() not in (1, self.B) or not sigma.is_contiguous() or str(sigma.dtype) != "torch.float64":
+                raise SlkError(f"{what}: sigma must hold 1 or {self.B} contiguous float64 values")
+            sa = _Arg(sigma.data_ptr(), 0 if sigma.numel() == 1 else 1, DEVICE if sigma.is_cuda else HOST, sigma)
+        else:
+            sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma, dtype=np.float64)).ravel())
+            if sg.size not in (1, self.B):
+                raise SlkError(f"{what}: sigma must hold 1 or {self.B} values, got {sg.size}")
+            sa = _Arg(sg.ctypes.data, 0 if sg.size == 1 else 1, HOST, sg)
+        if chi2 is None:
+            ca = _Arg(None, 0, None, None)
+        elif _is_dev(chi2):
+            if chi2.numel() < 2 * M - 2 or not chi2.is_contiguous() or str(chi2.dtype) != "torch.float64":
+                raise SlkError(f"{what}: chi2 must hold {2 * M - 2} contiguous float64 values")
+            ca = _Arg(chi2.data_ptr(), 0, DEVICE if chi2.is_cuda else HOST, chi2)
+        else:
+            ch = np.ascontiguousarray(chi2, dtype=np.float64).ravel()
+            if ch.size < 2 * M - 2:
+                raise SlkError(f"{what}: chi2 must hold {2 * M - 2} values (indexed by 2 n_obs - 3), got {ch.size}")
+            ca = _Arg(ch.ctypes.data, 0, HOST, ch)
+        where = _where(ta, sa, ca)
+        if where == DEVICE:
+            import torch
+            torch.cuda.current_stream(tracks.device).synchronize()   # (the handle's stream does not wait for torch's)
+        return ta, sa, ca, J, M, where
+
+    def track_linearize(self, tracks, sigma, m, chi2=None):
+        """(r [B, m], H [B, m, N], feat [B, J, 4]) of the feature tracks at the resident mean (slk_track_linearize): each
+        track is triangulated from the window's poses and projected onto the left null space of its landmark Jacobian;
+        rows j (2M - 3) .. of track j, whitened by sigma, so that update_ekf(r, 0, H, I, gate=False) is the update.
+        feat[b, j] = (X, flag): 1 used, 0 unused, -1 failed, -2 gated out by chi2 (indexed by 2 n_obs - 3).  The filter
+        is not modified.  numpy -> numpy; device tensors -> device tensors, H a [B, m, N] view of the column-major storage
+        as ekf_linearize() returns it."""
+        B, N, m = self.B, self.N, int(m)
+        ta, sa, ca, J, M, where = self._track_args(tracks, sigma, chi2, "track_linearize")
+        if where == DEVICE:
+            import torch
+            r = torch.empty((B, m), dtype=torch.float64, device=tracks.device)
+            Hs = torch.empty((B, N, m), dtype=torch.float64, device=tracks.device)
+            feat = torch.empty((B, J, 4), dtype=torch.float64, device=tracks.device)
+            _check(self._lib.slk_track_linearize(self._h, ta.ptr, ta.stride, J, M, sa.ptr, sa.stride, ca.ptr, m, r.data_ptr(),
+                                                 Hs.data_ptr(), feat.data_ptr(), DEVICE), "slk_track_linearize")
+            self.sync()                                        # torch may read the outputs on any stream
+            return r, Hs.transpose(1, 2), feat
+        r, Hs, feat = np.empty((B, m)), np.empty((B, N, m)), np.empty((B, J, 4))
+        _check(self._lib.slk_track_linearize(self._h, ta.ptr, ta.stride, J, M, sa.ptr, sa.stride, ca.ptr, m, r.ctypes.data,
+                                             Hs.ctypes.data, feat.ctypes.data, HOST), "slk_track_linearize")
+        return r, np.ascontiguousarray(np.transpose(Hs, (0, 2, 1))), feat
+
+    def update_tracks(self, tracks, sigma, m, chi2=None):
+        """The multi-state-constraint update from feature tracks (slk_update_tracks): track_linearize() into a workspace
+        of the handle, then the EKF update on it -- bit-identical to track_linearize() + update_ekf(r, 0, H, I,
+        gate=False) on device tensors, with nothing leaving the device.  Returns feat [B, J, 4] (numpy or device tensor,
+        as the tracks are).  A filter without a used track stays bit for bit what it was."""
+        ta, sa, ca, J, M, where = self._track_args(tracks, sigma, chi2, "update_tracks")
+        feat, fptr = self._feat_out(tracks, J, where)
+        _check(self._lib.slk_update_tracks(self._h, ta.ptr, ta.stride, J, M, sa.ptr, sa.stride, ca.ptr, int(m), fptr, where),
+               "slk_update_tracks")
+        if where == DEVICE:
+            self.sync()
+        return feat
+
+    def step_tracks(self, pmodel, u, Q, tracks, sigma, m, chi2=None):
+        """predict() followed by update_tracks(), bit for bit, in one call (slk_step_tracks)."""
+        ua = _rows(u, self.B, 7 if pmodel == PM_CONST_VELOCITY else 13)
+        qa = _mat(Q, self.B, 12)
+        ta, sa, ca, J, M, where = self._track_args(tracks, sigma, chi2, "step_tracks")
+        if _where(ua, qa) != where:
+            raise SlkError("all arguments of one call must live on the same side (host or device)")
+        feat, fptr = self._feat_out(tracks, J, where)
+        _check(self._lib.slk_step_tracks(self._h, pmodel, ua.ptr, ua.stride, qa.ptr, qa.stride, ta.ptr, ta.stride, J, M,
+                                         sa.ptr, sa.stride, ca.ptr, int(m), fptr, where), "slk_step_tracks")
+        if where == DEVICE:
+            self.sync()
+        return feat
+
+    def _feat_out(self, tracks, J, where):
+        if where == DEVICE:
+            import torch
+            feat = torch.empty((self.B, J, 4), dtype=torch.float64, device=tracks.device)
+            return feat, feat.data_ptr()
+        feat = np.empty((self.B, J, 4))
+        return feat, feat.ctypes.data
 
     def checkSigmaPoints(self):
         """checkSigmaPoints() (Msckf.hpp:819-839) on the device: returns (max |covSigmaPoints - Pk| [B],
