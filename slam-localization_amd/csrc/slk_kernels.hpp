@@ -583,9 +583,18 @@ struct CholPSteps {
         if constexpr (JK < NT) {
             constexpr int LDC = CholM<NT>::LDC;
             constexpr int k0 = 16 * JK + C0;
-            if (OUT == 2 || k0 < n) {
+            if (k0 < n) {
                 const int c = lane & 15, g = lane >> 4;
                 const int row = (NT == 4) ? lane : min(lane, 16 * NT - 1);
+                // The tile variant (OUT == 2, n known when the kernel is compiled) trims what nothing reads.  Column k0 + p of
+                // a partially live step (k0 < n <= k0 + 3) is padding when k0 + p >= n: it is published with its tile row, but
+                // it is neither read back, nor pivoted, nor eliminated, nor tested.  (Untrimmed its pivot could not fire
+                // either: cholm_load_t pads with a unit diagonal and zeros elsewhere, the padding rows of the live columns
+                // stay exact zeros through every scale and multiply-add, so the padding block stays the identity and each
+                // of its pivots is exactly 1 -- unless an earlier pivot already failed and raised the flag itself.)
+                auto live = [&](int p) { return OUT != 2 || k0 + p < n; };
+                // the last live step of the matrix: no later step publishes, so no fragment and no trailing update is needed
+                const bool last = OUT == 2 && k0 + 4 >= n;
                 // 1. publish the four pivot columns, raw (the accumulators hold -A, tiles transposed: cholm_load_t): register
                 // C0 / 4 of lane (g, c) is element (16 I + c, k0 + g)
 #pragma unroll
@@ -594,9 +603,10 @@ struct CholPSteps {
                 // 2. this lane's row of the panel, and the four columns
                 double l[4];
 #pragma unroll
-                for (int p = 0; p < 4; ++p) l[p] = -colbuf[p * LDC + row];
+                for (int p = 0; p < 4; ++p) l[p] = live(p) ? -colbuf[p * LDC + row] : 0.0;
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
+                    if (!live(p)) continue;
                     const double d = readlane_f64(l[p], k0 + p);
                     {   // (tested here and now: left alone the compiler keeps all sixty pivots for one test at the end -- in scalar
                         // registers it does not have, i.e. spilled lane by lane; the flag goes through a vector register)
@@ -609,15 +619,18 @@ struct CholPSteps {
                     (void)sq;
                     l[p] *= rs;                                   // (lane k0 + p held the pivot: d * rs = sqrt(d))
 #pragma unroll
-                    for (int q = p + 1; q < 4; ++q) l[q] = fma(-l[p], readlane_f64(l[p], k0 + q), l[q]);
+                    for (int q = p + 1; q < 4; ++q)
+                        if (live(q)) l[q] = fma(-l[p], readlane_f64(l[p], k0 + q), l[q]);
                 }
                 // (rows above the diagonal of the pivot block and retired rows carry garbage: as fragments they only reach
                 // accumulator slots that are dead after this step, and the packed factor takes rows >= column only)
                 // 3. the factor panel: to LDS for the fragments, to the packed factor from the row layout
-                wave_sync();
-                if (NT == 4 || lane < 16 * NT) {
+                if (!last) {
+                    wave_sync();
+                    if (NT == 4 || lane < 16 * NT) {
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) colbuf[p * LDC + lane] = l[p];
+                        for (int p = 0; p < 4; ++p) colbuf[p * LDC + lane] = l[p];
+                    }
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
@@ -638,17 +651,31 @@ struct CholPSteps {
                         if (k0 + p < n && lane >= k0 + p && lane < n) Lp[pkcol(n, k0 + p) + lane] = l[p];
                     }
                 }
-                wave_sync();
-                double frag[NT];
+                if (!last) {
+                    // tile column JK retires with its fourth step: nothing publishes from it again, so its trailing update
+                    // and the fragment only it multiplies by are left out there (every variant: C0 is a template argument;
+                    // the optimiser finds these ten dead updates by itself -- 70 MFMAs per factorisation at NT = 4, not 80 --
+                    // this says so in the source)
+                    constexpr int J0 = (C0 == 12) ? JK + 1 : JK;
+                    wave_sync();
+                    double frag[NT];
 #pragma unroll
-                for (int I = JK; I < NT; ++I) frag[I] = colbuf[g * LDC + 16 * I + c];
-                wave_sync();       // the next step's publish must not overtake these reads
-                // 4. rank-4 update of the trailing tiles (the tiles the next step publishes first)
+                    for (int I = J0; I < NT; ++I) frag[I] = colbuf[g * LDC + 16 * I + c];
+                    wave_sync();       // the next step's publish must not overtake these reads
+                    // 4. rank-4 update of the trailing tiles (the tiles the next step publishes first)
 #pragma unroll
-                for (int J = JK; J < NT; ++J)
+                    for (int J = J0; J < NT; ++J)
 #pragma unroll
-                    for (int I = J; I < NT; ++I)
-                        acc[tile_idx(I, J)] = __builtin_amdgcn_mfma_f64_16x16x4f64(frag[J], frag[I], acc[tile_idx(I, J)], 0, 0, 0);   // (tile^T += L_J L_I^T)
+                        for (int I = J; I < NT; ++I)
+                            acc[tile_idx(I, J)] = __builtin_amdgcn_mfma_f64_16x16x4f64(frag[J], frag[I], acc[tile_idx(I, J)], 0, 0, 0);   // (tile^T += L_J L_I^T)
+                }
+            } else if constexpr (OUT == 2) {
+                // a step all of whose columns are padding: the zeros the tile layout promises, and nothing else
+                if (lane >= 16 * JK && (NT == 4 || lane < 16 * NT)) {
+                    const int It = lane >> 4;
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) Lp[(It * (It + 1) / 2 + JK) * 256 + (C0 + p) * 16 + (lane & 15)] = 0.0;
+                }
             }
             CholPSteps<NT, (C0 == 12 ? JK + 1 : JK), (C0 + 4) & 15, OUT>::run(acc, Lp, n, colbuf, lane, bad);
         }
