@@ -447,13 +447,11 @@ __global__ __launch_bounds__(NTHREADS) void msckf_ekf_tile_kernel(EkfArgs a)
                         if (tail <= 2.2250738585072014e-308) { tk = 0.0; beta = cc0; rden = 0.0; }
                         else {
                             // beta = -sign(c0) |x|, tau = (beta - c0) / beta = 1 + |c0| / |x|, 1 / (c0 - beta) =
-                            // sign(c0) / (|c0| + |x|): one reciprocal square root and one reciprocal, Newton-refined
+                            // sign(c0) / (|c0| + |x|): one reciprocal square root and one reciprocal, refined
                             double nrm, rnrm;
                             rsqrt_pivot(cc0 * cc0 + tail, nrm, rnrm);
                             const double ac = fabs(cc0), sg = (cc0 >= 0.0) ? 1.0 : -1.0, dd = ac + nrm;
-                            double rr = __builtin_amdgcn_rcp(dd);
-                            rr = rr * fma(-dd, rr, 2.0);
-                            rr = rr * fma(-dd, rr, 2.0);
+                            const double rr = rcp_refined(dd);
                             beta = -sg * nrm;
                             tk = fma(ac, rnrm, 1.0);
                             rden = sg * rr;

@@ -286,7 +286,7 @@ __device__ __forceinline__ void rot_deviation(const double *mu, const double *re
 // Lower Cholesky of an n x n matrix with the trailing matrix held in REGISTERS, block-cyclic over a
 // GD x GD thread grid (thread (ti,tj) owns elements i = ti + GD*sa, j = tj + GD*sb).  Per column: the
 // owners publish the raw column through a double-buffered LDS vector, ONE barrier, everybody applies
-// a_ij -= c_i c_j / d.  The pivot uses v_rsq_f64 + two Newton steps instead of sqrt and two divisions
+// a_ij -= c_i c_j / d.  The pivot uses v_rsq_f64 + one third-order step instead of sqrt and two divisions
 // (they were the critical path).  The finished factor goes to the packed array Lp.  init(i, j)
 // supplies the initial lower-triangle element (global memory, or P minus the gain downdate), so no
 // copy of P is staged in LDS.  Returns -1 or the first non-positive pivot (same in every thread).
@@ -295,10 +295,14 @@ template <int NTHREADS> struct Grid { static constexpr int GD = (NTHREADS >= 256
 
 __device__ __forceinline__ void rsqrt_pivot(double d, double &sq, double &rs)
 {
-    double y = __builtin_amdgcn_rsq(d);
-    double h = 0.5 * d;
-    y = y * fma(-h * y, y, 1.5);
-    y = y * fma(-h * y, y, 1.5);
+    // one third-order step from the seed y0 (relative error 5e-8): with r = 1 - d y0^2,
+    // 1 / sqrt(d) = y0 (1 + r / 2 + 3 r^2 / 8 + O(r^3)), the neglected term ~1e-21.  Five operations on four dependent
+    // levels (p and yr are independent of each other) where two Newton steps took seven on six.
+    const double y0 = __builtin_amdgcn_rsq(d);
+    const double t = d * y0;
+    const double r = fma(-t, y0, 1.0);
+    const double p = fma(0.375, r, 0.5), yr = y0 * r;
+    const double y = fma(yr, p, y0);
     sq = d * y;                             // sqrt(d): y is 1/sqrt(d) to about an ulp already
     rs = y;
 }
@@ -570,7 +574,7 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
 // tile rows, then pick one of the four results: ~250 vector instructions per step, and one wave per filter runs at
 // the rate of its instruction count (msckf_chol_kernel: 3.9 k per filter, 46 us per 4096 filters).  Here the four
 // published columns are read back with lane = ROW (one value per column), the 64 x 4 panel is factored once for all
-// rows -- per column: pivot by v_readlane, v_rsq_f64 + two Newton steps, one scale, one multiply-add per remaining
+// rows -- per column: pivot by v_readlane, v_rsq_f64 + one third-order step, one scale, one multiply-add per remaining
 // panel column -- written to LDS again and fetched as the matrix-core fragments of the rank-4 update; the packed factor
 // is stored straight from the row layout.  A non-positive pivot is recorded; what follows it is never used.
 // OUT: where the factor goes -- 0: packed, LDS; 1: packed, global memory; 2: the 16 x 16 tiles of the exact-shape update kernel
@@ -694,7 +698,7 @@ __device__ __forceinline__ int cholp_factor(d4 (&acc)[CholM<NT>::NTL], double *L
 
 // ------------------------------------------------------------------ one-wave register Cholesky of a small matrix
 // lane = row, the row's NMAX columns in registers (n <= NMAX <= 32 rows live).  Per column: the pivot by v_readlane, its
-// inverse square root (v_rsq_f64 + two Newton steps), one scale, and per trailing column one broadcast (v_readlane) and
+// inverse square root (v_rsq_f64 + one third-order step), one scale, and per trailing column one broadcast (v_readlane) and
 // one multiply-add -- a single wave runs at the rate of its instruction count (an fp64 operation issues every ~10.6
 // cycles whether or not it depends on the one before: profiles/r01_mfma_valu_overlap.log), so the count is what is
 // minimised.  No LDS round trip, no branch: a non-positive pivot is recorded (what follows it is never used).

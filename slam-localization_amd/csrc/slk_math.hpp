@@ -94,6 +94,15 @@ __device__ __forceinline__ Quat so3_exp(double vx, double vy, double vz)
     return Quat{m * vx, m * vy, m * vz, c};
 }
 
+// 1 / a from the v_rcp_f64 seed r0 by one second-order step: with e = 1 - a r0, 1 / a = r0 (1 + e + e^2 + O(e^3)).
+// Three operations where two Newton steps took four; to about an ulp either way (tools/micro/rsq_precision.hip).
+__device__ __forceinline__ double rcp_refined(double a)
+{
+    const double r0 = __builtin_amdgcn_rcp(a);
+    const double e = fma(-a, r0, 1.0);
+    return fma(fma(e, e, e), r0, r0);
+}
+
 // MTK::SO3::log: 2 atan(|vec|/w)/|vec| * vec (|vec| clamped to 1e-11).  With u = |vec|/w the factor is
 // 2/w * atan(u)/u and atan(u)/u = sum (-u^2)^k/(2k+1): for u^2 < 1/16 (rotation below ~28 deg) the
 // series is replaced by a polynomial of degree 8 in u^2 (near-minimax, < 1 ulp) -- one reciprocal instead of sqrt + 2 divisions + atan.
@@ -104,10 +113,8 @@ __device__ __forceinline__ void so3_log(const Quat &q, double &vx, double &vy, d
     const double w2 = q.w * q.w;
     double s;
     if (q.w > 0.0 && n2 * 16.0 < w2) {
-        // 1 / w by v_rcp_f64 and two Newton steps (to about an ulp) instead of the IEEE division sequence
-        double rw = __builtin_amdgcn_rcp(q.w);
-        rw = fma(fma(-q.w, rw, 1.0), rw, rw);
-        rw = fma(fma(-q.w, rw, 1.0), rw, rw);
+        // 1 / w by v_rcp_f64 and one second-order step (to about an ulp) instead of the IEEE division sequence
+        const double rw = rcp_refined(q.w);
         const double y = -(n2 * rw * rw);
         double f = 0x1.78be0a9b1dd1fp-5;          // atan(u) / u, degree 8 in y: near-minimax (tools/series_coefficients.py), relative error 9e-18
         f = fma(f, y, 0x1.0b3340fe2ed9ap-4);
@@ -168,8 +175,8 @@ __device__ __forceinline__ Quat update_attitude(double dt, const double *w0, con
     const double qx = 0.75 * w0[0] * dt - 0.25 * w1[0] * dt + (1.0 / 24.0) * cx * dt2 - k * w0[0];
     const double qy = 0.75 * w0[1] * dt - 0.25 * w1[1] * dt + (1.0 / 24.0) * cy * dt2 - k * w0[1];
     const double qz = 0.75 * w0[2] * dt - 0.25 * w1[2] * dt + (1.0 / 24.0) * cz * dt2 - k * w0[2];
-    const double nrm = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-    return Quat{qx / nrm, qy / nrm, qz / nrm, qw / nrm};
+    const double rn = rcp_refined(sqrt(qw * qw + qx * qx + qy * qy + qz * qz));      // (one reciprocal, not four division sequences)
+    return Quat{qx * rn, qy * rn, qz * rn, qw * rn};
 }
 // DeadReckon::updatePose delta pose (src/core/DeadReckon.hpp:129-239): u = dt v0[3] w0[3] v1[3] w1[3] ->
 // d = dpos[3] dquat[4] velocity[3] angular_velocity[3] (the input of the delta-pose process model)

@@ -185,9 +185,7 @@ __device__ __forceinline__ bool so3_log_tab(const double *T, const Quat (&q)[NV]
     if (!wide) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            double r = __builtin_amdgcn_rcp(q[i].w);
-            r = fma(fma(-q[i].w, r, 1.0), r, r);
-            r = fma(fma(-q[i].w, r, 1.0), r, r);
+            const double r = rcp_refined(q[i].w);
             sc[i] = 2.0 * r;                         // log(q) = 2 / w * [atan(u) / u] * vec
             y[i] = -(y[i] * r * r);
         }
@@ -195,20 +193,15 @@ __device__ __forceinline__ bool so3_log_tab(const double *T, const Quat (&q)[NV]
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const double n2 = y[i], aw = fabs(q[i].w);
-            double r = __builtin_amdgcn_rcp(1.0 + aw);
-            r = fma(fma(-(1.0 + aw), r, 1.0), r, r);
-            r = fma(fma(-(1.0 + aw), r, 1.0), r, r);
+            const double r = rcp_refined(1.0 + aw);
             double k = r, t2 = n2 * r * r;           // tan(theta / 4) = k |vec|, its square
 #pragma unroll
             for (int rep = 0; rep < 2; ++rep) {      // t <- t / (1 + sqrt(1 + t^2))
                 const double a1 = 1.0 + t2;
-                double rs = __builtin_amdgcn_rsq(a1);
-                rs = rs * fma(-0.5 * a1 * rs, rs, 1.5);
-                rs = rs * fma(-0.5 * a1 * rs, rs, 1.5);
+                double sq, rs;
+                rsqrt_pivot(a1, sq, rs);
                 const double den = fma(a1, rs, 1.0);  // 1 + sqrt(1 + t^2)
-                double rd = __builtin_amdgcn_rcp(den);
-                rd = fma(fma(-den, rd, 1.0), rd, rd);
-                rd = fma(fma(-den, rd, 1.0), rd, rd);
+                const double rd = rcp_refined(den);
                 k *= rd;
                 t2 *= rd * rd;
             }
@@ -645,9 +638,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             // (x / z by one refined reciprocal and a correction step: within an ulp of the IEEE quotient, half the instructions
             // of two divisions)
             auto quot = [](double lx_, double ly_, double lz_, double &q0, double &q1) __attribute__((always_inline)) {
-                double r = __builtin_amdgcn_rcp(lz_);
-                r = fma(fma(-lz_, r, 1.0), r, r);
-                r = fma(fma(-lz_, r, 1.0), r, r);
+                const double r = rcp_refined(lz_);
                 q0 = lx_ * r; q0 = fma(fma(-lz_, q0, lx_), r, q0);
                 q1 = ly_ * r; q1 = fma(fma(-lz_, q1, ly_), r, q1);
             };
@@ -663,7 +654,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         dZi[f * 128 + 2 * j] = yp0 - ym0; dZi[f * 128 + 2 * j + 1] = yp1 - ym1;
         const double s0 = wave_sum_f64(yp0 + ym0), s1 = wave_sum_f64(yp1 + ym1);
         if (lane == 0) {                                        // mean_z (:234) about Z_0, innovation (:236)
-            const double e0 = s0 / (double)S, e1 = s1 / (double)S;
+            const double e0 = s0 * (1.0 / (double)S), e1 = s1 * (1.0 / (double)S);
             innov[2 * f] = a.z[(size_t)bidx * 8 + 2 * f] - (Z00 + e0);
             innov[2 * f + 1] = a.z[(size_t)bidx * 8 + 2 * f + 1] - (Z01 + e1);
             dz0[2 * f] = e0; dz0[2 * f + 1] = e1;

@@ -382,9 +382,7 @@ __global__ __launch_bounds__(64, UPRED_WAVES) void usckf_predict_kernel(KArgs a)
 #pragma unroll
                 for (int p = r + 1; p < 12; ++p) s -= Lblk[pk(12, p, r)] * fk[p];
                 const double dgl = Lblk[pk(12, r, r)];
-                double rd = __builtin_amdgcn_rcp(dgl);       // reciprocal by two Newton steps (to about an ulp) instead of the division sequence
-                rd = fma(fma(-dgl, rd, 1.0), rd, rd);
-                rd = fma(fma(-dgl, rd, 1.0), rd, rd);
+                const double rd = rcp_refined(dgl);          // refined reciprocal (to about an ulp) instead of the division sequence
                 fk[r] = s * rd;
                 __builtin_amdgcn_sched_barrier(0);           // (one row of the factor in flight at a time: registers)
             }
