@@ -450,6 +450,60 @@ __device__ __forceinline__ void cholm_load_t(d4 (&acc)[CholM<NT>::NTL], int n, i
             }
 }
 
+// cholm_load_t of an N x N matrix in global memory, N a compile-time constant (lower triangle read, column-major).  Left to an
+// element lambda the forty loads of N = 60 take 68 64-bit vector additions for their addresses.  Here an address is a
+// wave-uniform base in scalar registers, one per tile column (the column's offsets lie within the +-4 KB immediate range about
+// it), a 32-bit lane offset -- ONE for every tile below the diagonal (row 16 I + c, column 16 J + g + 4 r: c + g N bytes-scaled),
+// four for the diagonal tiles, where the lane reads (max, min) of its (row, column) -- and an immediate.  Lanes in the padding
+// (rows / columns >= N of the last tile row) read element (0, 0) of the tile column and take the unit diagonal / zero instead.
+template <int NT, int N>
+__device__ __forceinline__ void cholm_load_t_exact(d4 (&acc)[CholM<NT>::NTL], const double *gP, int lane)
+{
+    static_assert(N > 16 * (NT - 1) && N <= 16 * NT, "N fills NT tile rows");
+    constexpr int RL = N - 16 * (NT - 1);                     // live rows of the last tile row
+    constexpr bool PADDED = RL < 16;
+    constexpr long MID = 2560;                                // bytes: the column's offsets span 0 .. 8 (3 N 4 + 48) about its base
+    static_assert(8L * (12 * N + 16 * (NT - 1) + 16) - MID < 4096 && MID <= 4096, "one base per tile column");
+    const int c = lane & 15, g = lane >> 4;
+    const unsigned below = 8u * (unsigned)(c + g * N);
+    const bool rowin = !PADDED || c < RL;
+    unsigned diag[4], diagl[4];
+    bool din[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int cc = g + 4 * r, hi = c > cc ? c : cc, lo = c > cc ? cc : c;
+        diag[r] = 8u * (unsigned)(hi + lo * N);
+        din[r] = !PADDED || hi < RL;
+        diagl[r] = din[r] ? diag[r] : 0u;
+    }
+#pragma unroll
+    for (int J = 0; J < NT; ++J) {
+        // (pinned in scalar registers, and as a GLOBAL pointer: through an integer it would come back as a flat one)
+        typedef __attribute__((address_space(1))) const char gchar;
+        typedef __attribute__((address_space(1))) const double gcdouble;
+        unsigned long long pin = reinterpret_cast<unsigned long long>(gP) + (8L * 16 * J * N + MID);
+        asm volatile("" : "+s"(pin));
+        gchar *sb = reinterpret_cast<gchar *>(pin);
+#pragma unroll
+        for (int I = J; I < NT; ++I)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool lastrow = PADDED && I == NT - 1;
+                double v;
+                if (I == J) {
+                    gchar *lp = sb + (lastrow ? diagl[r] : diag[r]);
+                    v = *reinterpret_cast<gcdouble *>(lp + (8L * 16 * J - MID));
+                    if (lastrow) v = din[r] ? v : (c == g + 4 * r ? 1.0 : 0.0);
+                } else {
+                    gchar *lp = sb + (lastrow && !rowin ? 0u : below);
+                    v = *reinterpret_cast<gcdouble *>(lp + (8L * (16 * I + 4 * r * N) - MID));
+                    if (lastrow) v = rowin ? v : 0.0;
+                }
+                acc[tile_idx(I, J)][r] = -v;                  // the accumulators hold -A: the rank-4 updates ADD L L^T
+            }
+    }
+}
+
 // acc -= X * Y^T with X, Y n x kk column-major panels in LDS (ld ldx / ldy); column c of X is xcol(c)
 template <int NT, class XFn, class YFn>
 __device__ __forceinline__ void cholm_downdate(d4 (&acc)[CholM<NT>::NTL], int n, int kk, int lane, XFn xel, YFn yel)
@@ -569,6 +623,32 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
 }
 
+// Four LDS stores of one wave under lane masks that are compile-time constants: v[p] goes to addr + OFF + 128 p (bytes) on the
+// lanes LO + p <= lane < HI, on no lane where that range is empty.  A mask the compiler derives from `lane >= k` costs a
+// vector compare, a save and a restore of EXEC and a branch per store; here EXEC is a field of ones from one scalar
+// instruction (s_bfm_b64: width, position), saved and restored once for the four.  To be called where the whole wave is
+// active (wave-local code under wave-uniform branches only: EXEC is REPLACED, not narrowed -- the one caller is wave 0's
+// factorisation); the stores count on lgkmcnt like any other -- the caller's wave_sync() retires them.
+template <int LO, int HI, int OFF>
+__device__ __forceinline__ void lds_store4_lane_ranges(unsigned addr, const double (&v)[4])
+{
+    constexpr int W0 = HI - LO > 0 ? HI - LO : 0, W1 = HI - LO - 1 > 0 ? HI - LO - 1 : 0;
+    constexpr int W2 = HI - LO - 2 > 0 ? HI - LO - 2 : 0, W3 = HI - LO - 3 > 0 ? HI - LO - 3 : 0;
+    static_assert(LO >= 0 && HI <= 64 && W0 < 64 && LO + 3 < 64 && OFF >= 0 && OFF + 384 < 65536, "s_bfm_b64 fields, ds offset");
+    unsigned long long save;
+    asm volatile("s_mov_b64 %[sv], exec\n\t"
+                 "s_bfm_b64 exec, %[w0], %[l0]\n\tds_write_b64 %[a], %[v0] offset:%[o0]\n\t"
+                 "s_bfm_b64 exec, %[w1], %[l1]\n\tds_write_b64 %[a], %[v1] offset:%[o1]\n\t"
+                 "s_bfm_b64 exec, %[w2], %[l2]\n\tds_write_b64 %[a], %[v2] offset:%[o2]\n\t"
+                 "s_bfm_b64 exec, %[w3], %[l3]\n\tds_write_b64 %[a], %[v3] offset:%[o3]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [sv] "=&s"(save)
+                 : [a] "v"(addr), [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]),
+                   [w0] "n"(W0), [w1] "n"(W1), [w2] "n"(W2), [w3] "n"(W3), [l0] "n"(LO), [l1] "n"(LO + 1), [l2] "n"(LO + 2), [l3] "n"(LO + 3),
+                   [o0] "n"(OFF), [o1] "n"(OFF + 128), [o2] "n"(OFF + 256), [o3] "n"(OFF + 384)
+                 : "memory");
+}
+
 // ------------------------------------------------------------------ the same blocked factorisation, panel by rows
 // cholm_factor's step has every lane redo the 4 x 4 pivot block and forward-substitute four columns for each of its
 // tile rows, then pick one of the four results: ~250 vector instructions per step, and one wave per filter runs at
@@ -580,13 +660,15 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
 // OUT: where the factor goes -- 0: packed, LDS; 1: packed, global memory; 2: the 16 x 16 tiles of the exact-shape update kernel
 // (slk_step_fast.hpp: tile (I, J) at (I (I + 1) / 2 + J) * 256, element (t, j) at (j & 15) * 16 + (t & 15), exact zeros above the
 // diagonal and in the padding), LDS
-template <int NT, int JK, int C0, int OUT = 1>
+template <int NT, int JK, int C0, int OUT = 1, int NC = 0>
 struct CholPSteps {
-    __device__ __forceinline__ static void run(d4 (&acc)[CholM<NT>::NTL], double *Lp, int n, double *colbuf, int lane, bool &bad)
+    __device__ __forceinline__ static void run(d4 (&acc)[CholM<NT>::NTL], double *Lp, int n, double *colbuf, int lane, unsigned &bad)
     {
+        static_assert(OUT != 2 || (NC > 0 && NC <= 16 * NT), "the tile variant takes n as a template argument too");
         if constexpr (JK < NT) {
             constexpr int LDC = CholM<NT>::LDC;
             constexpr int k0 = 16 * JK + C0;
+            if constexpr (OUT == 2) n = NC;                 // (the tile variant: ONE n, the compile-time one, for pivots and masks)
             if (k0 < n) {
                 const int c = lane & 15, g = lane >> 4;
                 const int row = (NT == 4) ? lane : min(lane, 16 * NT - 1);
@@ -604,54 +686,72 @@ struct CholPSteps {
 #pragma unroll
                 for (int I = JK; I < NT; ++I) colbuf[g * LDC + 16 * I + c] = acc[tile_idx(I, JK)][C0 / 4];
                 wave_sync();
-                // 2. this lane's row of the panel, and the four columns
-                double l[4];
+                // 2. this lane's row of the panel, and the four columns.  The published values stay as they are, m = -A (a
+                // v_readlane takes no modifier, so a negation after the LDS read is an instruction of its own per element):
+                // the pivot changes sign on the scalar side, the scale is l = m * (-rs) and the columns not yet scaled take
+                // m_q <- fma(l_p, b, m_q) = -fma(-l_p, b, -m_q) -- every l is the double it would be with the sign taken first
+                double m[4], l[4];
 #pragma unroll
-                for (int p = 0; p < 4; ++p) l[p] = live(p) ? -colbuf[p * LDC + row] : 0.0;
+                for (int p = 0; p < 4; ++p) m[p] = live(p) ? colbuf[p * LDC + row] : 0.0;
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
+                    l[p] = 0.0;
                     if (!live(p)) continue;
-                    const double d = readlane_f64(l[p], k0 + p);
+                    const double mpiv = readlane_f64(m[p], k0 + p), d = -mpiv;
                     {   // (tested here and now: left alone the compiler keeps all sixty pivots for one test at the end -- in scalar
-                        // registers it does not have, i.e. spilled lane by lane; the flag goes through a vector register)
-                        int nb = !(d > 0.0);
-                        asm volatile("" : "+v"(nb));
-                        bad |= (nb != 0);
+                        // registers it does not have, i.e. spilled lane by lane.  The pivot is wave-uniform: in the tile variant the
+                        // test is integer arithmetic on its two halves, pivot_rank_neg in slk_math.hpp, and the flag -- the
+                        // largest rank so far -- one scalar register.  The packed variants keep the vector compare, the flag through
+                        // a vector register: with the scalar form the Usckf step ran 0.4 % behind in two sessions -- inside
+                        // the scatter, so not settled: profiles/ab_chain_trim.log)
+                        if constexpr (OUT == 2) {
+                            const unsigned rk = pivot_rank_neg((unsigned)__double2hiint(mpiv), (unsigned)__double2loint(mpiv));
+                            bad = rk > bad ? rk : bad;
+                            asm volatile("" : "+s"(bad));
+                        } else {
+                            int nb = !(d > 0.0);
+                            asm volatile("" : "+v"(nb));
+                            bad |= (nb != 0) ? 0x7ff00000u : 0u;
+                        }
                     }
                     double sq, rs;
                     rsqrt_pivot(d, sq, rs);
                     (void)sq;
-                    l[p] *= rs;                                   // (lane k0 + p held the pivot: d * rs = sqrt(d))
+                    l[p] = m[p] * -rs;                            // (lane k0 + p held the pivot: d * rs = sqrt(d))
 #pragma unroll
                     for (int q = p + 1; q < 4; ++q)
-                        if (live(q)) l[q] = fma(-l[p], readlane_f64(l[p], k0 + q), l[q]);
+                        if (live(q)) m[q] = fma(l[p], readlane_f64(l[p], k0 + q), m[q]);
                 }
                 // (rows above the diagonal of the pivot block and retired rows carry garbage: as fragments they only reach
                 // accumulator slots that are dead after this step, and the packed factor takes rows >= column only)
-                // 3. the factor panel: to LDS for the fragments, to the packed factor from the row layout
-                if (!last) {
+                // 3. the factor panel: to LDS for the fragments, to the packed factor from the row layout.  The tile variant
+                // keeps ONE copy: each column goes to its tile under the lane mask row >= column (rows < n) -- the tiles were
+                // zero-filled before the factorisation began (see cholp_factor), so the zeros above the diagonal and in the
+                // padding are there already -- and the fragments are read from the tiles
+                if constexpr (OUT != 2) {
                     wave_sync();
                     if (NT == 4 || lane < 16 * NT) {
 #pragma unroll
                         for (int p = 0; p < 4; ++p) colbuf[p * LDC + lane] = l[p];
                     }
                 }
+                if constexpr (OUT == 2) {
+                    typedef __attribute__((address_space(3))) double ldouble;
+                    const int It = lane >> 4;
+                    const unsigned trow = (unsigned)(size_t)(ldouble *)Lp + (It * (It + 1) / 2 * 256 + (lane & 15)) * 8;     // element (lane, 0) of tile (It, 0)
+                    lds_store4_lane_ranges<k0, NC, (JK * 256 + C0 * 16) * 8>(trow, l);
+                }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     // (the column's base pinned in scalar registers: the store is `global_store v_lane8, data, s[base]` -- left to
                     // itself the compiler keeps ONE base and adds every column's offset with 64-bit vector arithmetic)
-                    if constexpr (OUT == 2) {
-                        if (lane >= 16 * JK && (NT == 4 || lane < 16 * NT)) {
-                            const int It = lane >> 4;
-                            Lp[(It * (It + 1) / 2 + JK) * 256 + (C0 + p) * 16 + (lane & 15)] = (k0 + p < n && lane >= k0 + p) ? l[p] : 0.0;
-                        }
-                    } else if constexpr (OUT == 1) {
+                    if constexpr (OUT == 1) {
                         typedef __attribute__((address_space(1))) double gdouble;
                         unsigned long long colb = reinterpret_cast<unsigned long long>(Lp + pkcol(n, k0 + p));
                         asm volatile("" : "+s"(colb));
                         gdouble *colp = reinterpret_cast<gdouble *>(colb);
                         if (k0 + p < n && lane >= k0 + p && lane < n) colp[lane] = l[p];
-                    } else {
+                    } else if constexpr (OUT == 0) {
                         if (k0 + p < n && lane >= k0 + p && lane < n) Lp[pkcol(n, k0 + p) + lane] = l[p];
                     }
                 }
@@ -663,9 +763,20 @@ struct CholPSteps {
                     constexpr int J0 = (C0 == 12) ? JK + 1 : JK;
                     wave_sync();
                     double frag[NT];
+                    if constexpr (OUT == 2) {
+                        // element (16 I + c, k0 + g) of the tiles.  Where the panel copy held garbage (rows above the diagonal of
+                        // the pivot block) the tiles hold exact zeros.  That concerns tile column JK only, and only while it still
+                        // takes an update (C0 < 12): column j of tile (I, JK) gets sum_g L(j, k0 + g) L(i, k0 + g) with
+                        // L(j, k0 + g) read as zero for j < k0 + g -- columns j <= k0 + 3, all retired with this step; the live
+                        // columns j >= k0 + 4 multiply entries below the diagonal, the same doubles as in the panel copy.
+                        // (no wait after these reads: the next publish stores accumulators that the updates below write)
 #pragma unroll
-                    for (int I = J0; I < NT; ++I) frag[I] = colbuf[g * LDC + 16 * I + c];
-                    wave_sync();       // the next step's publish must not overtake these reads
+                        for (int I = J0; I < NT; ++I) frag[I] = Lp[tile_idx(I, JK) * 256 + (C0 + g) * 16 + c];
+                    } else {
+#pragma unroll
+                        for (int I = J0; I < NT; ++I) frag[I] = colbuf[g * LDC + 16 * I + c];
+                        wave_sync();       // the next step's publish must not overtake these reads
+                    }
                     // 4. rank-4 update of the trailing tiles (the tiles the next step publishes first)
 #pragma unroll
                     for (int J = J0; J < NT; ++J)
@@ -673,27 +784,22 @@ struct CholPSteps {
                         for (int I = J; I < NT; ++I)
                             acc[tile_idx(I, J)] = __builtin_amdgcn_mfma_f64_16x16x4f64(frag[J], frag[I], acc[tile_idx(I, J)], 0, 0, 0);   // (tile^T += L_J L_I^T)
                 }
-            } else if constexpr (OUT == 2) {
-                // a step all of whose columns are padding: the zeros the tile layout promises, and nothing else
-                if (lane >= 16 * JK && (NT == 4 || lane < 16 * NT)) {
-                    const int It = lane >> 4;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) Lp[(It * (It + 1) / 2 + JK) * 256 + (C0 + p) * 16 + (lane & 15)] = 0.0;
-                }
             }
-            CholPSteps<NT, (C0 == 12 ? JK + 1 : JK), (C0 + 4) & 15, OUT>::run(acc, Lp, n, colbuf, lane, bad);
+            // (OUT == 2: a step all of whose columns are padding stores nothing -- its zeros are the fill's)
+            CholPSteps<NT, (C0 == 12 ? JK + 1 : JK), (C0 + 4) & 15, OUT, NC>::run(acc, Lp, n, colbuf, lane, bad);
         }
     }
 };
 
 // factor the matrix held in `acc` (see cholm_load_t: TRANSPOSED tiles); wave-local, returns -1 or 0 (some pivot was not positive)
-template <int NT, int OUT = 1>
+// (OUT == 2: n = NC, and the caller has zero-filled the NT (NT + 1) / 2 tiles of Lp -- the columns are stored below the diagonal only)
+template <int NT, int OUT = 1, int NC = 0>
 __device__ __forceinline__ int cholp_factor(d4 (&acc)[CholM<NT>::NTL], double *Lp, int n, double *colbuf, int lane)
 {
-    bool bad = false;
-    CholPSteps<NT, 0, 0, OUT>::run(acc, Lp, n, colbuf, lane, bad);
+    unsigned bad = 0u;                          // the largest pivot_rank so far
+    CholPSteps<NT, 0, 0, OUT, NC>::run(acc, Lp, n, colbuf, lane, bad);
     wave_sync();
-    return bad ? 0 : -1;
+    return pivot_rank_not_positive(bad) ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ one-wave register Cholesky of a small matrix
@@ -2010,6 +2116,7 @@ __global__ __launch_bounds__(NTHREADS, (NTHREADS >= 256 && NT >= 3 && NT <= 4 ? 
     constexpr bool BIG = NT > 4;                           // large state (N > 64): factor + rotation store in the global workspace
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if constexpr (HasFastStep<NT, NTHREADS, KST, MST>::value) {
+        static_assert(NTHREADS == 256, "msckf_step_fast is written for four waves (its tile fill, its wave roles)");
         if (!a.do_predict && a.do_update && msckf_step_fast<KST>(a, smem)) return;
     }
     constexpr int NW = NTHREADS / 64;

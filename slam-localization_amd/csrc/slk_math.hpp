@@ -34,6 +34,30 @@ __device__ __forceinline__ void qrot(const Quat &q, double vx, double vy, double
     oz = vz + q.w * uz + (q.x * uy - q.y * ux);
 }
 
+// !(d > 0.0) from the two 32-bit halves of d, for every bit pattern: the pivot test of a factorisation whose pivot is
+// wave-uniform (a v_readlane pair), in integer arithmetic on the scalar side.  As a 64-bit integer u the positive doubles
+// are 1 .. 0x7ff0000000000000 (denormals, normal numbers, +inf); everything else -- +0, the NaNs above +inf and every
+// pattern with the sign bit: -0, negative numbers, -inf, NaNs -- is not.  So d > 0.0 <=> u - 1 < 0x7ff0000000000000, and the
+// upper half of u - 1 decides: rank = hi - (lo == 0) (the borrow) = hi - 1 + (lo != 0), not positive <=> rank >= 0x7ff00000.
+// The factorisations hold -A, so the pivot is d = -x with x read from the accumulators: pivot_rank_neg takes the halves of x
+// (flipping the sign bit adds 2^31 to the upper half: xhi + 2^31 - 1 + (xlo != 0)).  On the device it is the carry chain it
+// is -- SCC = (xlo != 0), one add with carry; the compiler's own lowering of the expression copies the carry through a
+// 64-bit mask and back, five instructions -- and its operands must be wave-uniform (scalar registers).  A factorisation keeps
+// the largest rank of its pivots (one scalar maximum per pivot) and tests that once.
+__host__ __device__ __forceinline__ unsigned pivot_rank_neg(unsigned xhi, unsigned xlo)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned rk;
+    asm("s_cmp_lg_u32 %2, 0\n\ts_addc_u32 %0, %1, 0x7fffffff" : "=s"(rk) : "s"(xhi), "s"(xlo) : "scc");
+    return rk;
+#else
+    return xhi + 0x7fffffffu + (xlo != 0u ? 1u : 0u);
+#endif
+}
+__host__ __device__ __forceinline__ bool pivot_rank_not_positive(unsigned rank) { return rank >= 0x7ff00000u; }
+// the predicate on the halves of d itself (x = -d: the sign bit flipped)
+__host__ __device__ __forceinline__ bool pivot_not_positive(unsigned hi, unsigned lo) { return pivot_rank_not_positive(pivot_rank_neg(hi ^ 0x80000000u, lo)); }
+
 // MTK cos_sinc_sqrt(x) = (cos(sqrt x), sin(sqrt x)/sqrt x).  Both are entire functions of x:
 //   cos(sqrt x) = sum (-x)^k/(2k)!,   sin(sqrt x)/sqrt x = sum (-x)^k/(2k+1)!
 // For x < 1/4 (rotation below 1 rad, the usual sigma-point spread) polynomials of degree 6 / 5 in x stand for the

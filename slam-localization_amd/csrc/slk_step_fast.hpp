@@ -281,21 +281,28 @@ __device__ __forceinline__ bool fast_ldm_columns(double (&Gf)[36], const double 
                                                  double *Wb, double *mdiag)
 {
     const bool live = lane < N;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const bool kr = (kept >> r) & 1u;
-#pragma unroll
-        for (int c = 0; c <= r; ++c) {
-            const bool in = kr && ((kept >> c) & 1u);
-            const double sv = Sm[in ? r + 8 * c : 0];
-            SLK_G(r, c) = in ? sv - SLK_G(r, c) : ((r == c) ? 1.0 : 0.0);
-        }
-    }
+    // set-up: T_j = S - G_j over the surviving rows, identity rows for the rejected ones -- column j of it at step j of the
+    // chain below, where it is first read.  kept is wave-uniform and nearly always 0xff: that case takes the plain loads and
+    // subtractions (no select, no select-addressed LDS read per entry) behind a uniform branch; the chain itself is ONE copy
+    // of code.  (All 36 entries set up ahead of the chain in two forms: the kernel spills -- 44 registers, 128 B of scratch.)
+    const bool full = kept == 0xffu;
     // T_j = R R^T in place (R lower, its diagonal kept as reciprocals), y = R^-1 b, d = 1 - |y|^2, w = -R^-T y / sqrt(d)
     double y[8];
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
+        if (full) {
+#pragma unroll
+            for (int r = j; r < 8; ++r) SLK_G(r, j) = Sm[r + 8 * j] - SLK_G(r, j);
+        } else {
+            const bool kj = (kept >> j) & 1u;
+#pragma unroll
+            for (int r = j; r < 8; ++r) {
+                const bool in = kj && ((kept >> r) & 1u);
+                const double sv = Sm[in ? r + 8 * j : 0];
+                SLK_G(r, j) = in ? sv - SLK_G(r, j) : ((r == j) ? 1.0 : 0.0);
+            }
+        }
         double d = SLK_G(j, j);
 #pragma unroll
         for (int p = 0; p < j; ++p) d = fma(-SLK_G(j, p), SLK_G(j, p), d);
@@ -537,6 +544,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     using F = FastShape<K>;
     constexpr int N = F::N, Nq = F::Nq, S = F::S, NSO3 = F::NSO3, NT = F::NT, NKS = F::NKS, NROT = F::NROT;
     constexpr int NP = F::NP;
+    constexpr int NTHREADS = 256;                                // four waves (HasFastStep: the only block size that gets here)
     if (a.mm != SLK_MM_FEATURE_PROJ || a.gate == 2 || a.emit != 0 || a.rebuild_prec != 0 || !a.mp || a.m != 8) return false;
     const int bidx = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -602,10 +610,18 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             }
         }
         // (after the stores above: the sixteen loaded values must not live across this region)
-        if (here && wave == 0) {
+        if (here) {
+            // wave 0 issues its loads of P, the other three (idle from here to the barrier of phase 0) zero-fill the tiles, and
+            // one barrier puts the fill before wave 0's first tile store: the factorisation then stores a column under the
+            // lane mask row >= column alone, and reads its rank-4 fragments back from the tiles (CholPSteps, OUT == 2)
             d4 fa[CholM<NT>::NTL];
-            cholm_load_t<NT>(fa, N, lane, [&](int i, int j) { return gP[i + (size_t)j * N]; });
-            bad |= cholp_factor<NT, 2>(fa, Lt, N, U, lane) >= 0;      // (the union region is free until phase 1: its colbuf)
+            if (wave == 0) cholm_load_t_exact<NT, N>(fa, gP, lane);
+            else {
+                double2 *Lt2 = reinterpret_cast<double2 *>(Lt);
+                for (int e = tid - 64; e < CholM<NT>::NTL * 128; e += NTHREADS - 64) Lt2[e] = double2{0.0, 0.0};   // (every wave but wave 0)
+            }
+            __syncthreads();
+            if (wave == 0) bad |= cholp_factor<NT, 2, N>(fa, Lt, N, U, lane) >= 0;   // (the union region is free until phase 1: its colbuf)
         }
     }
     if (__syncthreads_or(bad)) SLK_FBAIL(2);
@@ -741,14 +757,25 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     __syncthreads();
     if (wave == 0) {
         double gg[8][8], gi[8], y[8];
+        // (set-up with every row kept -- kept is wave-uniform and nearly always 0xff -- without the selects; one chain for both.
+        // The innovation keeps its select inside the chain: held here it is eight more doubles live beside the 36 entries)
+        if (kept == 0xffu) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+            for (int i = 0; i < 8; ++i) {
 #pragma unroll
-            for (int j = 0; j <= i; ++j) {
-                const bool in = ((kept >> i) & 1u) && ((kept >> j) & 1u);
-                const double v = Sm[in ? i + 8 * j : 0];
-                gg[i][j] = in ? v : (i == j ? 1.0 : 0.0);
+                for (int j = 0; j <= i; ++j) gg[i][j] = Sm[i + 8 * j];
             }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+#pragma unroll
+                for (int j = 0; j <= i; ++j) {
+                    const bool in = ((kept >> i) & 1u) && ((kept >> j) & 1u);
+                    const double v = Sm[in ? i + 8 * j : 0];
+                    gg[i][j] = in ? v : (i == j ? 1.0 : 0.0);
+                }
+            }
+        }
         bool spd = true;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
