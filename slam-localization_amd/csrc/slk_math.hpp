@@ -58,6 +58,20 @@ __host__ __device__ __forceinline__ bool pivot_rank_not_positive(unsigned rank) 
 // the predicate on the halves of d itself (x = -d: the sign bit flipped)
 __host__ __device__ __forceinline__ bool pivot_not_positive(unsigned hi, unsigned lo) { return pivot_rank_not_positive(pivot_rank_neg(hi ^ 0x80000000u, lo)); }
 
+// The manifold mean's stop rule |mean_delta| > 1e-6 (reference Msckf.hpp:511) on the SQUARED norm s, without the square root:
+// the largest double whose correctly rounded square root is <= 1e-6.  With h = the midpoint of 1e-6 and the next double above it,
+// sqrt(s) rounds to at most 1e-6 exactly when s < h^2 (h^2 is no double), and this is the last double below h^2 -- so
+// s > MEAN_STOP_SQ is the same function of s as sqrt(s) > 1e-6 for every s, NaN included (both false).
+// tests/cpp/mean_stop_threshold.cpp checks it on the host.
+constexpr double MEAN_STOP_SQ = 0x1.19799812dea11p-40;
+
+// x < bound for a double x that is +0, positive, +inf or a NaN of either sign, from its upper dword alone and as an UNSIGNED
+// compare: bound's lower dword must be zero (then the lower dword of x cannot decide), the positive doubles order as their
+// bit patterns do, and every NaN has an upper dword >= 0x7ff00000, above any finite bound's -- false, as x < bound is.  The
+// largest upper dword of several such x answers for all of them at once (one v_max_u32 in place of a compare each).
+__host__ __device__ __forceinline__ bool nonneg_hi_below(unsigned xhi, unsigned bound_hi) { return xhi < bound_hi; }
+constexpr unsigned HI_QUARTER = 0x3fd00000u, HI_FOUR = 0x40100000u;      // upper dwords of 0.25 and 4.0
+
 // MTK cos_sinc_sqrt(x) = (cos(sqrt x), sin(sqrt x)/sqrt x).  Both are entire functions of x:
 //   cos(sqrt x) = sum (-x)^k/(2k)!,   sin(sqrt x)/sqrt x = sum (-x)^k/(2k+1)!
 // For x < 1/4 (rotation below 1 rad, the usual sigma-point spread) polynomials of degree 6 / 5 in x stand for the

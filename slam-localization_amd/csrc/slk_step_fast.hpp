@@ -57,6 +57,7 @@ template <int K> struct FastShape {
     static constexpr int oStr = oCq + 40;                      // the two odd parts of row 15 that fall into tile (0, 1)
     static constexpr int oInts = oStr + 64;                    // 64 ints
     static constexpr int oTab = oInts + 32;                    // series coefficients (26)
+    static constexpr int oMsq = oTab + 28;                     // the two partial sums of |mean_delta|^2 (in the table's unused tail)
     static constexpr int oU = oTab + 32;                       // union region
     // union, phases 1 - 5: Yp [64][17] (rows [y+ ; y-] of a column, one double of padding: the lanes of a wave write
     // different banks; later W [512] and the parked prefix sums), dZ interleaved [512], Sm, mdiag, b, innov, dz0, tmpS
@@ -111,25 +112,22 @@ __device__ const double fast_series_table[26] = {
     0x1.78be0a9b1dd1fp-5, 0x1.0b3340fe2ed9ap-4, 0x1.3ab708d770276p-4, 0x1.7459b99bfc19bp-4, 0x1.c71c5f4b9c2adp-4, 0x1.24924907fa636p-3, 0x1.999999996d307p-3, 0x1.5555555555481p-2,
     0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
+// every active lane's p, as a wave-uniform value: the ballot of !p against zero -- one vector compare and the scalar test
+// (__all takes an int: a select and a compare of it on top)
+__device__ __forceinline__ bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }
+
 // q[i] = exp(v[i]) for NV rotation vectors.  Rotations below 1 rad (every lane of the wave): the series directly; otherwise
 // the series for v / 4 and two quaternion squarings, exp(v) = (exp(v / 4)^2)^2 -- up to 4 rad; ok = false beyond.
-template <int NV>
-__device__ __forceinline__ bool so3_exp_tab(const double *T, const double (&v)[NV][3], Quat (&q)[NV])
+// Two code paths behind the uniform branch, the series written out in each: merged into one with the halving selected in,
+// every call pays both squarings and six selects per argument.  The domain tests x < 1/4, x < 4 are taken on the largest
+// upper dword of the x (nonneg_hi_below, slk_math.hpp: x is a scaled sum of squares), the second on the halved path only
+// (x < 1/4 implies it).
+template <int NV, bool WIDE>
+__device__ __forceinline__ void so3_exp_tab_path(const double *T, const double (&v)[NV][3], const double (&x)[NV], Quat (&q)[NV])
 {
     double y[NV], cc[NV], ss[NV];
-    bool small = true, ok = true;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const double x = 0.25 * (v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2]);
-        small = small && (x < 0.25);
-        ok = ok && (x < 4.0);
-        y[i] = -x;
-    }
-    const bool wide = !__all(small);                 // (uniform over the wave)
-    if (wide) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) y[i] *= 0.0625;   // |v / 4|^2 / 4
-    }
+    for (int i = 0; i < NV; ++i) y[i] = WIDE ? -0.0625 * x[i] : -x[i];   // wide: |v / 4|^2 / 4
     {
         const double c0 = T[0], s0 = T[6];
 #pragma unroll
@@ -153,7 +151,7 @@ __device__ __forceinline__ bool so3_exp_tab(const double *T, const double (&v)[N
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         double m = 0.5 * ss[i], w = cc[i];           // exp(v) = (m v, w);  wide: exp(v / 4) = (m / 4 v, w)
-        if (wide) {
+        if (WIDE) {
             m *= 0.25;
 #pragma unroll
             for (int rep = 0; rep < 2; ++rep) {      // (w, m v)^2 = (2 w^2 - 1, 2 w m v) for a unit quaternion
@@ -164,7 +162,51 @@ __device__ __forceinline__ bool so3_exp_tab(const double *T, const double (&v)[N
         }
         q[i] = Quat{m * v[i][0], m * v[i][1], m * v[i][2], w};
     }
-    return ok;
+}
+// FLAG: an argument beyond 4 rad in any lane sets *flag where it is found, on the halved path (the result is true then);
+// else the lane's own ok is the result
+template <int NV, bool FLAG>
+__device__ __forceinline__ bool so3_exp_tab_impl(const double *T, const double (&v)[NV][3], Quat (&q)[NV], int *flag)
+{
+    double x[NV];
+    unsigned hm = 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        x[i] = 0.25 * (v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2]);
+        const unsigned hi = (unsigned)__double2hiint(x[i]);
+        hm = hi > hm ? hi : hm;
+    }
+    if (wave_all(nonneg_hi_below(hm, HI_QUARTER))) { // (uniform over the wave)
+        so3_exp_tab_path<NV, false>(T, v, x, q);
+        return true;
+    }
+    so3_exp_tab_path<NV, true>(T, v, x, q);
+    const bool ok = nonneg_hi_below(hm, HI_FOUR);
+    if (!FLAG) return ok;
+    if (!wave_all(ok)) *flag = 1;
+    return true;
+}
+// a * b for b = an exponential of so3_exp_tab: qmul's products and sums with the contraction written out, from the left.  Left
+// to the compiler, which of the two products of `a.w * b.x + a.x * b.w` is rounded before the other is fused onto it depends on
+// where b.w comes from (one code path or two): one rounding per component that moved with the code around it.
+__device__ __forceinline__ Quat qmul_exp(const Quat &a, const Quat &b)
+{
+    Quat o;
+    o.w = fma(-a.z, b.z, fma(-a.y, b.y, fma(a.w, b.w, -(a.x * b.x))));
+    o.x = fma(-a.z, b.y, fma(a.y, b.z, fma(a.x, b.w, a.w * b.x)));
+    o.y = fma(-a.x, b.z, fma(a.z, b.x, fma(a.y, b.w, a.w * b.y)));
+    o.z = fma(-a.y, b.x, fma(a.x, b.y, fma(a.z, b.w, a.w * b.z)));
+    return o;
+}
+template <int NV>
+__device__ __forceinline__ bool so3_exp_tab(const double *T, const double (&v)[NV][3], Quat (&q)[NV])
+{
+    return so3_exp_tab_impl<NV, false>(T, v, q, nullptr);
+}
+template <int NV>
+__device__ __forceinline__ void so3_exp_tab_flag(const double *T, const double (&v)[NV][3], Quat (&q)[NV], int *flag)
+{
+    so3_exp_tab_impl<NV, true>(T, v, q, flag);
 }
 // d[i] = log(q[i]) in MTK's form 2 atan(|vec| / w) / |vec| * vec (q and -q give the same result).  Rotations below ~28
 // degrees (every lane of the wave): the series of atan(u) / u directly, u = |vec| / w.  Otherwise by halved angles:
@@ -177,11 +219,13 @@ __device__ __forceinline__ bool so3_log_tab(const double *T, const Quat (&q)[NV]
     bool small = true;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        const double n2 = q[i].x * q[i].x + q[i].y * q[i].y + q[i].z * q[i].z, w2 = q[i].w * q[i].w;
-        small = small && (q[i].w > 0.0) && (n2 * 16.0 < w2);
+        // w > 0 and 16 n2 < w^2 in one compare: w |w| is w^2 with the sign of w (the same product, the same rounding), and
+        // 16 n2 >= +0 is below nothing that is negative, a zero or a NaN
+        const double n2 = q[i].x * q[i].x + q[i].y * q[i].y + q[i].z * q[i].z, ws = q[i].w * fabs(q[i].w);
+        small = small && (n2 * 16.0 < ws);
         y[i] = n2;
     }
-    const bool wide = !__all(small);                 // (uniform over the wave)
+    const bool wide = !wave_all(small);              // (uniform over the wave)
     if (!wide) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -552,7 +596,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     double *Lt = smem + F::oLt, *mu = smem + F::oMu, *ref = smem + F::oRef, *delta = smem + F::oDelta, *md32 = smem + F::oMd;
     double *d0 = smem + F::oD0, *d0s = smem + F::oD0s, *pd = smem + F::oPd, *cq = smem + F::oCq, *str = smem + F::oStr, *U = smem + F::oU;
     int *ints = reinterpret_cast<int *>(smem + F::oInts);          // [0..39] gate lists of the waves, [48] [49] flags
-    double *T = smem + F::oTab;
+    double *T = smem + F::oTab, *msq = smem + F::oMsq;
     double *Yp = U + F::uYp, *Wb = U + F::uW, *dZi = U + F::uDZ, *Sm = U + F::uSm, *mdiag = U + F::uMdiag, *bvec = U + F::uB;
     double *innov = U + F::uInnov, *dz0 = U + F::uDz0, *tmpS = U + F::uTmp, *Et = U;
     const double *gmean = a.mean + (size_t)bidx * Nq;
@@ -648,7 +692,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         {
             const double rv[2][3] = {{l[3], l[4], l[5]}, {-l[3], -l[4], -l[5]}};
             Quat ex[2];
-            if (!__all(so3_exp_tab<2>(T, rv, ex))) ints[50] = 1; // a rotation column beyond the series' domain (1 rad)
+            so3_exp_tab_flag<2>(T, rv, ex, ints + 50);               // (set by a rotation column beyond the series' domain, 4 rad)
             const Quat qx = Quat{x[3], x[4], x[5], x[6]};
             double lx, ly, lz;
             // (x / z by one refined reciprocal and a correction step: within an ulp of the IEEE quotient, half the instructions
@@ -658,9 +702,9 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
                 q0 = lx_ * r; q0 = fma(fma(-lz_, q0, lx_), r, q0);
                 q1 = ly_ * r; q1 = fma(fma(-lz_, q1, ly_), r, q1);
             };
-            qrot(qconj(qmul(qx, ex[0])), fx - (x[0] + l[0]), fy - (x[1] + l[1]), fz - (x[2] + l[2]), lx, ly, lz);
+            qrot(qconj(qmul_exp(qx, ex[0])), fx - (x[0] + l[0]), fy - (x[1] + l[1]), fz - (x[2] + l[2]), lx, ly, lz);
             quot(lx, ly, lz, zp0, zp1);
-            qrot(qconj(qmul(qx, ex[1])), fx - (x[0] - l[0]), fy - (x[1] - l[1]), fz - (x[2] - l[2]), lx, ly, lz);
+            qrot(qconj(qmul_exp(qx, ex[1])), fx - (x[0] - l[0]), fy - (x[1] - l[1]), fz - (x[2] - l[2]), lx, ly, lz);
             quot(lx, ly, lz, zm0, zm1);
         }
         const double Z00 = readlane_f64(zp0, 63), Z01 = readlane_f64(zp1, 63);       // lanes >= tp + 6 evaluate X_0
@@ -839,8 +883,8 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             const Quat qm = ldq(mu + so);
             const double dv[1][3] = {{delta[to], delta[to + 1], delta[to + 2]}};
             Quat ex[1];
-            if (!so3_exp_tab<1>(T, dv, ex)) ints[50] = 1;
-            const Quat qr = qmul(qm, ex[0]);
+            so3_exp_tab_flag<1>(T, dv, ex, ints + 50);
+            const Quat qr = qmul_exp(qm, ex[0]);
             stq(ref + so, qr);
             stq(cq + 4 * lane, qmul(qconj(qr), qm));
         }
@@ -902,9 +946,9 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             const double rv[2][3] = {{e0 + l0, e1 + l1, e2 + l2}, {e0 - l0, e1 - l1, e2 - l2}};
             Quat ex[2];
             double dd[2][3];
-            bool ok = so3_exp_tab<2>(T, rv, ex);
-            ex[0] = qmul(cb, ex[0]);
-            ex[1] = qmul(cb, ex[1]);
+            so3_exp_tab_flag<2>(T, rv, ex, ints + 50);          // (set beyond the series' domain; the log has none)
+            ex[0] = qmul_exp(cb, ex[0]);
+            ex[1] = qmul_exp(cb, ex[1]);
 #ifdef SLK_STAMPS
             {   // diagnostic: which waves leave the direct series (bit 0 / 1 of round r: exp / log went the angle-halving way)
                 bool se = true, sl = true;
@@ -918,8 +962,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
                 if (lane == 0 && a.dbg && it == 0) a.dbg[(size_t)bidx * 32 + slot] = (r ? a.dbg[(size_t)bidx * 32 + slot] : 0) | (code << (2 * r));
             }
 #endif
-            ok = so3_log_tab<2>(T, ex, dd) && ok;
-            if (!__all(ok)) ints[50] = 1;                        // beyond the series' domains
+            so3_log_tab<2>(T, ex, dd);
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) { dpl[r][cc] = dd[0][cc]; dmi[r][cc] = dd[1][cc]; }
             if (val[r]) {
@@ -933,10 +976,9 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             const Quat cb = ldq(cq + 4 * b);
             Quat ex[1];
             double dd[1][3];
-            bool ok = so3_exp_tab<1>(T, rv, ex);
-            ex[0] = qmul(cb, ex[0]);
-            ok = so3_log_tab<1>(T, ex, dd) && ok;
-            if (!__all(ok)) ints[50] = 1;
+            so3_exp_tab_flag<1>(T, rv, ex, ints + 50);
+            ex[0] = qmul_exp(cb, ex[0]);
+            so3_log_tab<1>(T, ex, dd);
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) {
                 dc[cc] = dd[0][cc];
@@ -957,21 +999,34 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             s += __shfl_xor(s, 16, 64);
             s += __shfl_xor(s, 32, 64);
             const int rho = 16 * hr + lane;                      // (lanes 0 .. 15 hold the sums of the rows 16 hr ..)
-            if (lane < 16 && rho < NROT) md32[rho] = (2.0 * s + d0s[rho]) * (1.0 / (double)S);
+            // |mean_delta|^2 where mean_delta is formed: each row of sixteen lanes sums its squares (four row shifts, lane 15
+            // ends with the row's sum; a wave without live rows -- wave 3 at k = 4 -- sums zeros), one partial sum per wave
+            double sq = 0.0;
+            if (lane < 16 && rho < NROT) {
+                const double mv = (2.0 * s + d0s[rho]) * (1.0 / (double)S);
+                md32[rho] = mv;
+                sq = mv * mv;
+            }
+            sq += dpp_mov_f64<0x111, 0xf>(sq);                   // row_shr:1
+            sq += dpp_mov_f64<0x112, 0xf>(sq);                   // row_shr:2
+            sq += dpp_mov_f64<0x114, 0xf>(sq);                   // row_shr:4
+            sq += dpp_mov_f64<0x118, 0xf>(sq);                   // row_shr:8
+            if (lane == 15) msq[hr] = sq;
         }
         __syncthreads();
-        const double mdl = (lane < NROT) ? md32[lane] : 0.0;
-        const double norm = sqrt(wave_sum_f64(mdl * mdl));
+        // every lane of every wave reads the same two doubles and adds them in the same order: one decision from the same
+        // bits, taken as a ballot (wave-uniform by construction; all lanes agree, so it is none or all of them)
+        const bool more = __builtin_amdgcn_ballot_w64(msq[0] + msq[1] > MEAN_STOP_SQ) != 0ull;   // :511, |mean_delta| > 1e-6 on the squared norm (slk_math.hpp)
         if (wave == 0 && lane < NSO3) {                          // reference += mean_delta (:510)
             const int so = lane ? 9 + 7 * lane : 3;
             const double dv[1][3] = {{md32[3 * lane], md32[3 * lane + 1], md32[3 * lane + 2]}};
             Quat ex[1];
-            if (!so3_exp_tab<1>(T, dv, ex)) ints[50] = 1;        // (a mean_delta beyond 1 rad)
-            const Quat qr = qmul(ldq(ref + so), ex[0]);
+            so3_exp_tab_flag<1>(T, dv, ex, ints + 50);           // (a mean_delta beyond 4 rad)
+            const Quat qr = qmul_exp(ldq(ref + so), ex[0]);
             stq(ref + so, qr);
             stq(cq + 4 * lane, qmul(qconj(qr), ldq(mu + so)));
         }
-        if (!(norm > 1e-6)) break;                               // :511
+        if (!more) break;
         if (++it >= 64) SLK_FBAIL(7);                            // (nothing has been written yet: the general body starts over)
         __syncthreads();
     }
