@@ -39,6 +39,14 @@ extern "C" {
 
 #define SLK_ABI_VERSION 1
 
+/* Msckf predict on the plain route (registered process model, no sigma-point emission): batches of at least this many
+ * filters run two filters per wave, smaller ones one filter per wave.  The results are bit-identical either way.  The value
+ * is the smallest batch from which the pair kernel measured ahead (profiles/ab_predict_pair.log): every batch that has a
+ * pair -- its in-row broadcasts issue less than the one-wave kernel's wave-wide ones even for a lone wave. */
+#ifndef SLK_PREDICT_PAIR_MIN_BATCH
+#define SLK_PREDICT_PAIR_MIN_BATCH 2
+#endif
+
 typedef struct slk_filter slk_filter;
 
 enum { SLK_MSCKF = 1, SLK_USCKF = 2 };
@@ -553,6 +561,11 @@ int slk_timer_stop(slk_filter *f, float *milliseconds);
 /* self test of the fp64 MFMA fragment layout used by the covariance rebuild: multiplies an
  * asymmetric 16x16 pair on the device and checks it on the host.  0 = layout as documented. */
 int slk_selftest_mfma(int device);
+
+/* self test of the two-filters-per-wave predict kernel on an odd batch of SLK_PREDICT_PAIR_MIN_BATCH | 1 filters (N = 12),
+ * on arrays of its own with guard words behind mean, P and status: 0 = every word the one-wave kernel's and the guards
+ * intact; else bit 0 = the kernels differ, bit 1 = a guard word was written, bit 2 = the case itself is off. */
+int slk_selftest_predict_pair(int device);
 
 #ifdef __cplusplus
 }

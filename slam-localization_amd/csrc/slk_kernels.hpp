@@ -623,6 +623,34 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
 }
 
+// Lane j of every DPP row (sixteen lanes) to all lanes of that row: v_mov_b64_dpp row_newbcast:j, one instruction, the
+// result in vector registers.  j must fold to a constant (fully unrolled callers).
+template <int J> __device__ __forceinline__ double row_bcast_const_f64(double x)
+{
+    return __builtin_amdgcn_update_dpp(0.0, x, 0x150 + J, 0xf, 0xf, true);
+}
+__device__ __forceinline__ double row_bcast_f64(double x, int j)
+{
+    switch (j & 15) {
+    case 0: return row_bcast_const_f64<0>(x);
+    case 1: return row_bcast_const_f64<1>(x);
+    case 2: return row_bcast_const_f64<2>(x);
+    case 3: return row_bcast_const_f64<3>(x);
+    case 4: return row_bcast_const_f64<4>(x);
+    case 5: return row_bcast_const_f64<5>(x);
+    case 6: return row_bcast_const_f64<6>(x);
+    case 7: return row_bcast_const_f64<7>(x);
+    case 8: return row_bcast_const_f64<8>(x);
+    case 9: return row_bcast_const_f64<9>(x);
+    case 10: return row_bcast_const_f64<10>(x);
+    case 11: return row_bcast_const_f64<11>(x);
+    case 12: return row_bcast_const_f64<12>(x);
+    case 13: return row_bcast_const_f64<13>(x);
+    case 14: return row_bcast_const_f64<14>(x);
+    default: return row_bcast_const_f64<15>(x);
+    }
+}
+
 // Four LDS stores of one wave under lane masks that are compile-time constants: v[p] goes to addr + OFF + 128 p (bytes) on the
 // lanes LO + p <= lane < HI, on no lane where that range is empty.  A mask the compiler derives from `lane >= k` costs a
 // vector compare, a save and a restore of EXEC and a branch per store; here EXEC is a field of ones from one scalar
@@ -811,11 +839,15 @@ __device__ __forceinline__ int cholp_factor(d4 (&acc)[CholM<NT>::NTL], double *L
 // 12 x 12: 6.1 k -> 4.6 k cycles including the load of the matrix (profiles/r03_ab_small_state_register_cholesky.log).
 // nst < n: the matrix is padded to n x n with a unit diagonal by the caller, the leading nst x nst part of the factor is stored
 // (packed for nst).
-template <int NMAX, class InitFn>
+// ROWB: the broadcasts stay inside each DPP row of sixteen lanes (row_bcast_f64) -- several matrices of NMAX <= 16 rows factor
+// side by side in one wave, one per DPP row, `lane` = the row of the caller's own matrix, Lp and init per matrix; the verdict
+// is then per lane (the same in the sixteen lanes of a DPP row).  Same operations on the same operands as the wave-wide form.
+template <int NMAX, bool ROWB = false, class InitFn>
 __device__ __forceinline__ int chol_rows(double *Lp, int n, int lane, InitFn init, int nst = -1)
 {
     if (nst < 0) nst = n;
     static_assert(NMAX <= 32, "chol_rows keeps a row per lane in registers");
+    static_assert(!ROWB || NMAX <= 16, "one matrix per DPP row of sixteen lanes");
     double a[NMAX];
 #pragma unroll
     for (int j = 0; j < NMAX; ++j) {
@@ -830,14 +862,14 @@ __device__ __forceinline__ int chol_rows(double *Lp, int n, int lane, InitFn ini
 #pragma unroll
     for (int j = 0; j < NMAX; ++j) {
         if (j < n) {
-            const double d = readlane_f64(a[j], j);
+            const double d = ROWB ? row_bcast_f64(a[j], j) : readlane_f64(a[j], j);
             bad |= !(d > 0.0);
             double sq, rs;
             rsqrt_pivot(d, sq, rs);
             (void)sq;
             a[j] *= rs;                               // (lane j held the pivot itself: d * rs = sqrt(d) as rsqrt_pivot forms it)
 #pragma unroll
-            for (int k = j + 1; k < NMAX; ++k) a[k] = fma(-a[j], readlane_f64(a[j], k), a[k]);
+            for (int k = j + 1; k < NMAX; ++k) a[k] = fma(-a[j], ROWB ? row_bcast_f64(a[j], k) : readlane_f64(a[j], k), a[k]);
             __builtin_amdgcn_sched_barrier(0);       // one column's broadcasts (scalar registers) at a time
         }
     }
@@ -3505,6 +3537,174 @@ __global__ __launch_bounds__(64, PRED_WAVES) void msckf_predict_kernel(KArgs a)
         if (tid < 13) gmean[tid] = mu[tid];
     }
     if (tid == 0 && st) atomicOr(a.status + bidx, st);
+}
+
+// ------------------------------------------------------------------ the Msckf predict kernel, two filters per wave
+// The plain route (registered process model, no emission) from SLK_PREDICT_PAIR_MIN_BATCH filters on.  A third of the one-wave
+// kernel's lanes idle (25 sigma points, 12 rows), and at four waves per SIMD (4096 filters) it is issue-bound, no latency chain.
+// Here half h = lane >> 5 of the wave owns filter 2 blockIdx.x + h with its own LDS carve; every per-filter piece of
+// predict_phase runs on the 32 lanes of its half (tid = lane & 31) with the SAME operations on the same operands in the same
+// order -- mean, the 12 x 12 block and status are bit-identical to msckf_predict_kernel's:
+//   * chol_rows<12, ROWB>: each filter's twelve rows sit in one DPP row of sixteen lanes, the pivots and trailing columns
+//     come from v_mov_b64_dpp row_newbcast (one instruction per double, where v_readlane took two);
+//   * the mean's four partial sums of 7 / 6 / 6 / 6 points: a lane forms two of them (s0, s1 or s2, s3) and their sum, one
+//     shuffle over the 16 lanes' distance gives (s0 + s1) + (s2 + s3); its twelve components again by row_newbcast;
+//   * the mean loop is a divergent loop: a half whose n2 has met the stop rule leaves it (EXEC), its registers and LDS stay
+//     as they were at its own exit, the other half iterates alone (every cross-lane operation stays inside a half);
+//   * a half whose 12 x 12 factorisation failed skips everything up to its status (SLK_ST_LLT_FAIL), its partner finishes;
+//   * the 16 x 16 matrix-core tile runs once per half on the whole wave with the one-wave kernel's code.
+// With odd B the upper half of the last wave has no filter: it shadows filter B - 1 for its loads and stores nothing.
+// LDS per half (doubles): mu 16, Lblk 80, Pn 144, Ys 326 (the deviation rows dbuf take its place once it is consumed), refs 16.
+constexpr int PRED_PAIR_WAVES = 4;      // waves per SIMD the pair kernel is compiled for (125 VGPRs, no scratch; 3 measured the same)
+constexpr int PRED_PAIR_HALF = 16 + 80 + 144 + 326 + 16;
+__global__ __launch_bounds__(64, PRED_PAIR_WAVES) void msckf_predict_pair_kernel(KArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double sm[2 * PRED_PAIR_HALF];
+    const int lane = threadIdx.x, h = lane >> 5, tid = lane & 31;
+    const int N = a.lay.N, Nq = a.lay.Nq;
+    const int fidx = 2 * blockIdx.x + h;
+    const bool live = fidx < a.B;
+    const int bidx = live ? fidx : a.B - 1;
+    double *hs = sm + h * PRED_PAIR_HALF;
+    double *mu = hs, *Lblk = hs + 16, *Pn = hs + 96, *Ys = hs + 240, *dbuf = Ys, *refs = hs + 566;
+    double *gmean = a.mean + (size_t)bidx * Nq;
+    double *gP = a.P + (size_t)bidx * N * N;
+    if (tid < 13) mu[tid] = gmean[tid];
+    wave_sync();
+    const int fail = chol_rows<12, true>(Lblk, 12, tid, [&](int i, int j) { return gP[i + (size_t)j * N]; });
+    // (lanes 16 .. 31 of a half factor copies of row 11 in a DPP row of their own: the verdict is the first row's)
+    const bool ok = !((__ballot(fail >= 0) >> (32 * h)) & 1ull);
+    const double *u = a.u ? a.u + (size_t)bidx * a.u_stride : nullptr;
+    if (ok && tid < 25) {
+        Sig s = sig_of(tid);
+        double v[12], x[13];
+#pragma unroll
+        for (int t = 0; t < 12; ++t) v[t] = pert(Lblk, 12, nullptr, t, s);
+        state_boxplus(mu, v, x);
+        process_model(a.pm, u, x, Ys + tid * 13);
+    }
+    wave_sync();
+    int it = 0, status = 0;
+    Quat rq = {0.0, 0.0, 0.0, 1.0};
+    if (ok) {
+        Quat q;
+        double dv[9], dr[3], mr[3];
+        {
+            const double *yrow = Ys + (tid < 25 ? tid : 0) * 13;
+            q = ldq(yrow + 3);
+            rq = ldq(Ys + 3);                                                        // reference = X[0]  (Msckf.hpp:473)
+#pragma unroll
+            for (int c = 0; c < 9; ++c) { const int sidx = c < 3 ? c : c + 4; dv[c] = yrow[sidx] - Ys[sidx]; }
+            if (tid < 13) refs[tid] = Ys[tid];
+        }
+        wave_sync();                                    // (Ys is consumed: dbuf takes its place)
+        double n2;
+        do {                                            // Msckf.hpp:478-487
+            so3_boxminus(q, rq, dr[0], dr[1], dr[2]);
+            if (tid < 25) {
+                double *row = dbuf + tid * 12;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { row[c] = dv[c]; row[3 + c] = dr[c]; }
+#pragma unroll
+                for (int c = 3; c < 9; ++c) row[3 + c] = dv[c];
+            }
+            wave_sync();
+            double mv[9];
+            {
+                // lane = pair of parts * 16 + component (components 12 .. 15 sum what follows their row: never used)
+                const int comp = tid & 15, p2 = tid >> 4;
+                const double *col = dbuf + 24 * p2 + comp;
+                double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { s0 += col[48 * i]; s1 += col[48 * i + 12]; }
+                const double last = dbuf[24 * 12 + comp];                   // point 24: the seventh of part 0
+                s0 = p2 == 0 ? s0 + last : s0;
+                double sum = s0 + s1;
+                sum += __shfl_xor(sum, 16, 64);
+                const double mc = sum * (1.0 / 25.0);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) mr[c] = row_bcast_f64(mc, 3 + c);
+#pragma unroll
+                for (int c = 0; c < 9; ++c) mv[c] = row_bcast_f64(mc, c < 3 ? c : c + 3);
+                if (tid < 12 && (tid < 3 || tid >= 6)) refs[tid < 3 ? tid : tid + 1] += mc;
+            }
+            n2 = ((mv[0] * mv[0] + mv[1] * mv[1]) + (mv[2] * mv[2] + mr[0] * mr[0]))
+               + ((mr[1] * mr[1] + mr[2] * mr[2]) + (mv[3] * mv[3] + mv[4] * mv[4]))
+               + ((mv[5] * mv[5] + mv[6] * mv[6]) + (mv[7] * mv[7] + mv[8] * mv[8]));
+            rq = qmul(rq, so3_exp(mr[0], mr[1], mr[2]));
+#pragma unroll
+            for (int c = 0; c < 9; ++c) dv[c] -= mv[c];
+            wave_sync();                                // (the next pass rewrites dbuf)
+        } while (n2 > 1e-12 && ++it < 10000);
+        if (it >= 10000) status |= SLK_ST_MEAN_NOT_CONVERGED;
+        if (tid < 25) {                                 // deviations against the final mean (predict_phase)
+            if (it < 10000) {
+                const double m0 = mr[0], m1 = mr[1], m2 = mr[2];
+                const double x = dr[0], y = dr[1], z = dr[2];
+                const double cx = y * m2 - z * m1, cy = z * m0 - x * m2, cz = x * m1 - y * m0;      // d x m
+                const double ax = y * cz - z * cy, ay = z * cx - x * cz, az = x * cy - y * cx;      // d x (d x m)
+                const double a12 = 1.0 / 12.0 + (x * x + y * y + z * z) * (1.0 / 720.0);
+                dr[0] = x - m0 + 0.5 * cx - a12 * ax;
+                dr[1] = y - m1 + 0.5 * cy - a12 * ay;
+                dr[2] = z - m2 + 0.5 * cz - a12 * az;
+            } else {
+                so3_boxminus(q, rq, dr[0], dr[1], dr[2]);
+            }
+            double *row = dbuf + tid * 12;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { row[c] = dv[c]; row[3 + c] = dr[c]; }
+#pragma unroll
+            for (int c = 3; c < 9; ++c) row[3 + c] = dv[c];
+        }
+    }
+    wave_sync();
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {    // 1/2 D D^T + Q per half on the whole wave (a failed half: never stored)
+        const double *db = sm + hh * PRED_PAIR_HALF + 240;
+        double *pn = sm + hh * PRED_PAIR_HALF + 96;
+        const int fb = min(2 * (int)blockIdx.x + hh, a.B - 1);
+        const double *Q = a.Q + (size_t)fb * a.q_stride;
+        const int fc = lane & 15, fg = lane >> 4;
+        double fr[7];
+#pragma unroll
+        for (int ks = 0; ks < 7; ++ks) {
+            const int i = 4 * ks + fg;
+            const bool in = fc < 12 && i < 25;
+            const double v = db[in ? i * 12 + fc : 0];
+            fr[ks] = in ? v : 0.0;
+        }
+        d4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = c0;
+#pragma unroll
+        for (int ks = 0; ks < 7; ++ks) {
+            if (ks & 1) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[ks], fr[ks], c1, 0, 0, 0);
+            else c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[ks], fr[ks], c0, 0, 0, 0);
+        }
+        c0 = c0 + c1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = fg + 4 * r;
+            if (row < 12 && fc < 12) pn[row + 12 * fc] = 0.5 * c0[r] + Q[row + 12 * fc];
+        }
+    }
+    if (ok) {
+        if (tid < 13 && (tid < 3 || tid >= 7)) mu[tid] = refs[tid];
+        if (tid == 0) stq(mu + 3, rq);
+    }
+    wave_sync();
+    // (the filter's index and addresses are formed again from a lane number the compiler cannot trace back: kept alive from
+    // the top of the kernel they cost five registers through every phase, and the register file limits the residency)
+    int lo = lane;
+    asm volatile("" : "+v"(lo));
+    const int fo = 2 * (int)blockIdx.x + (lo >> 5);
+    if (fo < a.B) {                                  // (the upper half of the last wave of an odd batch stores nothing)
+        if (ok) {                                    // a failed half: predict skipped, filter unchanged
+            double *oP = a.P + (size_t)fo * N * N, *omean = a.mean + (size_t)fo * Nq;
+            for (int e = tid; e < 144; e += 32) oP[(e % 12) + (size_t)(e / 12) * N] = Pn[e];
+            if (tid < 13) omean[tid] = mu[tid];
+        }
+        const int st = ok ? status : (int)SLK_ST_LLT_FAIL;
+        if (tid == 0 && st) atomicOr(a.status + fo, st);
+    }
 }
 
 #endif

@@ -22,6 +22,7 @@ MODEL_EXTERNAL, PM_CONST_VELOCITY, PM_DELTA_POSE, PM_DEAD_RECKON = 0, 1, 2, 3
 MM_VO_RELATIVE, MM_FEATURE_PROJ, MM_POSE_POSITION = 1, 2, 3
 ST_LLT_FAIL, ST_MEAN_NOT_CONVERGED, ST_SINGULAR, ST_ALL_REJECTED, ST_EKF_ROWS, ST_BAD_INDEX = 1, 2, 4, 8, 16, 32
 E_INVALID, E_NO_DEVICE, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5
+PREDICT_PAIR_MIN_BATCH = 2      # SLK_PREDICT_PAIR_MIN_BATCH of include/slk.h: Msckf predict runs two filters per wave from here on
 
 # every symbol include/slk.h declares (checked by the CPU test-suite against the built library)
 EXPORTS = [
@@ -30,7 +31,7 @@ EXPORTS = [
     "slk_step", "slk_predict_sigma_points", "slk_predict_from_sigma", "slk_update_sigma_points",
     "slk_update_from_sigma", "slk_usckf_cloning", "slk_usckf_set_measurement", "slk_msckf_resize",
     "slk_get_outliers", "slk_get_status", "slk_clear_status", "slk_sync", "slk_timer_start", "slk_timer_stop",
-    "slk_selftest_mfma", "slk_set_rebuild_precision", "slk_dead_reckon", "slk_msckf_clone_pose", "slk_msckf_drop_clone", "slk_update_ekf",
+    "slk_selftest_mfma", "slk_selftest_predict_pair", "slk_set_rebuild_precision", "slk_dead_reckon", "slk_msckf_clone_pose", "slk_msckf_drop_clone", "slk_update_ekf",
     "slk_check_sigma_points", "slk_update_innovation", "slk_update_selected", "slk_transform_compose",
     "slk_dead_reckon_pose", "slk_adaptive_create", "slk_adaptive_destroy", "slk_adaptive_matrix", "slk_nees",
     "slk_sample_states", "slk_step_n", "slk_step_n_slide", "slk_msckf_slide",
