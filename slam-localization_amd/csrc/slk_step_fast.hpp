@@ -18,7 +18,8 @@
 //         P+ = O O^T + E E^T + 1/2 d0 d0^T = O O^T + E^ E^^T + p d0^T + d0 p^T,   p = sum_j e^_j + (N + 1/2) / 2 d0,
 //     O and E^ are zero beyond column t + 2 of row t: tile column J of O O^T needs the k-steps 0 .. 4 J + 3 only, one wave
 //     per tile column, no cross-wave reduction; E^ E^^T is formed in the rotation-row space (three 16 x 16 tiles, 83 + 37
-//     MFMAs at k = 8) and added where the tiles leave for memory;
+//     MFMAs at k = 8), takes the rank-2 term (nonzero on rotation rows only) as one more k-step of each tile, and is added
+//     where the tiles leave for memory;
 //   * tiles leave from the accumulators (mirror triangle) and through a private LDS transpose (lower triangle).
 // Anything rare -- failed factorisation, rotation column beyond pi, non-SPD innovation covariance, every block gated out,
 // an indefinite downdate, a mean that needs more than 64 rounds, other models / gate modes -- returns false BEFORE the
@@ -387,6 +388,81 @@ __device__ __forceinline__ bool fast_ldm_columns(double (&Gf)[36], const double 
 }
 #undef SLK_G
 
+// Output tile (I, J) of the factor update -> the wave that computes it.  The tiles of one tile column share their M tiles
+// M(Kb, J) = dZ_Kb W_J^T (2 MFMAs each, formed once per wave and tile column; 4 more per (tile, Kb) for the product with
+// L(I, Kb)), so the map keeps tile columns together: the one with the fewest MFMAs in all among those whose longest wave is
+// no longer than under ldm_tile_wave (slk_kernels.hpp: 30 at NT = 4, 18 at NT = 3) -- tools/ldm_tile_assignment.py.
+// MFMAs per wave, JB = the last tile column that is not skipped:
+//   NT = 4   wave 0: (3,0) (0,0)   wave 1: (2,0) (1,0)   wave 2: (3,1) (2,1) (1,1)   wave 3: (3,2) (2,2) (3,3)
+//            JB = 3: 28 / 26 / 30 / 22 = 106 (ldm_tile_wave: 4 x 30)     JB = 2 (the benchmark): 22 / 26 / 24 / 10 = 82 (4 x 24)
+//            JB = 1: 16 / 20 / 14 / 0                                    JB = 0: 10 / 10 / 0 / 0
+//   NT = 3   wave 0: (1,0) (0,0)   wave 1: (2,1) (1,1)   wave 2: (2,0)   wave 3: (2,2)
+//            JB = 2: 16 / 16 / 18 / 6 = 56 (18 / 18 / 18 / 6)            JB = 1: 16 / 10 / 12 / 0     JB = 0: 10 / 0 / 6 / 0
+template <int NT> __host__ __device__ constexpr int fast_ldm_wave(int I, int J)
+{
+    if (NT == 4) return J == 0 ? ((I == 3 || I == 0) ? 0 : 1) : (J == 1 ? 2 : 3);
+    return J == 0 ? (I == 2 ? 2 : 0) : (J == 1 ? 1 : 3);
+}
+// position of tile (I, J) among the tiles of its wave: a compile-time accumulator index
+template <int NT> __host__ __device__ constexpr int fast_ldm_slot(int I, int J)
+{
+    int n = 0;
+    for (int i = 0; i < NT; ++i)
+        for (int j = 0; j <= i; ++j) {
+            if (i == I && j == J) return n;
+            if (fast_ldm_wave<NT>(i, j) == fast_ldm_wave<NT>(I, J)) ++n;
+        }
+    return n;
+}
+// does wave W own a tile (I, J) with I >= K0
+template <int NT> __host__ __device__ constexpr bool fast_ldm_owns(int W, int J, int K0)
+{
+    for (int i = (K0 > J ? K0 : J); i < NT; ++i)
+        if (fast_ldm_wave<NT>(i, J) == W) return true;
+    return false;
+}
+
+// the tiles of wave W: every M(Kb, J) once, then into each of the wave's tiles (I, J), I >= Kb -- per output element the
+// operations and their order (Kb ascending from J) of one tile at a time
+template <int NT, int W, int MAXT>
+__device__ __forceinline__ void fast_ldm_wave_tiles(const double *Lt, const double *dZi, const double *Wb, const double *mdiag, int lane,
+                                                    int JB, d4 (&acc)[MAXT])
+{
+    const int c = lane & 15, g = lane >> 4;
+    const int lw = (g >> 1) * 128 + 2 * c + (g & 1);           // lane part of bw_idx(16 X + c, g)
+#pragma unroll
+    for (int J = 0; J < NT; ++J) {
+        if (!fast_ldm_owns<NT>(W, J, J) || J > JB) continue;
+        const double wf0 = Wb[32 * J + lw], wf1 = Wb[256 + 32 * J + lw];
+#pragma unroll
+        for (int Kb = J; Kb < NT; ++Kb) {
+            if (!fast_ldm_owns<NT>(W, J, Kb) || Kb > JB) continue;
+            d4 mt = {0.0, 0.0, 0.0, 0.0};
+            const double a0 = dZi[32 * Kb + lw], a1 = dZi[256 + 32 * Kb + lw];
+            mt = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, wf0, mt, 0, 0, 0);
+            mt = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, wf1, mt, 0, 0, 0);
+            if (Kb == J) {
+                const double dg = mdiag[16 * J + c];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = g + 4 * r;
+                    mt[r] = (row > c) ? mt[r] : ((row == c) ? dg : 0.0);
+                }
+            }
+#pragma unroll
+            for (int I = Kb; I < NT; ++I) {
+                if (fast_ldm_wave<NT>(I, J) != W) continue;
+                double lf[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) lf[s] = Lt[(I * (I + 1) / 2 + Kb) * 256 + 64 * s + lane];
+                d4 &a = acc[fast_ldm_slot<NT>(I, J)];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) a = __builtin_amdgcn_mfma_f64_16x16x4f64(mt[s], lf[s], a, 0, 0, 0);
+            }
+        }
+    }
+}
+
 // L <- L M on the matrix cores, tiled factor (see ldm_product in slk_kernels.hpp for the algebra).  JB = tile column of the
 // last column any measurement row depends on: beyond it M is the identity (dZ rows are exactly zero), those blocks are
 // skipped.  fill() runs between the two barriers (everything but the factor is dead there).
@@ -394,49 +470,21 @@ template <int NT, class FillFn>
 __device__ __forceinline__ void ldm_product_tiled(double *Lt, const double *dZi, const double *Wb, const double *mdiag, int lane,
                                                   int wave, int JB, FillFn fill)
 {
-    const int c = lane & 15, g = lane >> 4;
-    const int lw = (g >> 1) * 128 + 2 * c + (g & 1);           // lane part of bw_idx(16 X + c, g)
-    constexpr int MAXT = (NT == 4) ? 4 : 2;
+    constexpr int MAXT = (NT == 4) ? 3 : 2;
     d4 acc[MAXT];
 #pragma unroll
     for (int q = 0; q < MAXT; ++q) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-        for (int J = 0; J <= I; ++J) {
-            if (ldm_tile_wave<NT>(I, J) != wave || J > JB) continue;
-            d4 a = {0.0, 0.0, 0.0, 0.0};
-            const double wf0 = Wb[32 * J + lw], wf1 = Wb[256 + 32 * J + lw];
-#pragma unroll
-            for (int Kb = J; Kb <= I; ++Kb) {
-                if (Kb > JB) continue;
-                d4 mt = {0.0, 0.0, 0.0, 0.0};
-                const double a0 = dZi[32 * Kb + lw], a1 = dZi[256 + 32 * Kb + lw];
-                double lf[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) lf[s] = Lt[(I * (I + 1) / 2 + Kb) * 256 + 64 * s + lane];
-                mt = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, wf0, mt, 0, 0, 0);
-                mt = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, wf1, mt, 0, 0, 0);
-                if (Kb == J) {
-                    const double dg = mdiag[16 * J + c];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = g + 4 * r;
-                        mt[r] = (row > c) ? mt[r] : ((row == c) ? dg : 0.0);
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) a = __builtin_amdgcn_mfma_f64_16x16x4f64(mt[s], lf[s], a, 0, 0, 0);
-            }
-            acc[ldm_tile_slot<NT>(I, J)] = a;
-        }
+    if (wave == 0) fast_ldm_wave_tiles<NT, 0>(Lt, dZi, Wb, mdiag, lane, JB, acc);
+    else if (wave == 1) fast_ldm_wave_tiles<NT, 1>(Lt, dZi, Wb, mdiag, lane, JB, acc);
+    else if (wave == 2) fast_ldm_wave_tiles<NT, 2>(Lt, dZi, Wb, mdiag, lane, JB, acc);
+    else fast_ldm_wave_tiles<NT, 3>(Lt, dZi, Wb, mdiag, lane, JB, acc);
     __syncthreads();                                  // every wave has read what it needs of the old factor
 #pragma unroll
     for (int I = 0; I < NT; ++I)
 #pragma unroll
         for (int J = 0; J <= I; ++J) {
-            if (ldm_tile_wave<NT>(I, J) != wave || J > JB) continue;
-            const d4 a = acc[ldm_tile_slot<NT>(I, J)];
+            if (fast_ldm_wave<NT>(I, J) != wave || J > JB) continue;
+            const d4 a = acc[fast_ldm_slot<NT>(I, J)];
 #pragma unroll
             for (int r = 0; r < 4; ++r) Lt[(I * (I + 1) / 2 + J) * 256 + 64 * r + lane] = a[r];
         }
@@ -476,6 +524,16 @@ __device__ __forceinline__ d4 fast_ee_tile(const double *Et, int lane)
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fi, fj, acc, 0, 0, 0);
     }
     return acc;
+}
+// ... + p d0^T + d0 p^T, the rank-2 term of P+, which lives on the rotation rows as well: one more k-step of the tile,
+// A = [p, d0, 0, 0], B = [d0, p, 0, 0] (pd = p [32], d0 [32]; rows from NROT on, pd[31] among them, are exact zeros)
+template <int HI, int HJ>
+__device__ __forceinline__ d4 fast_ee_rank2(const double *pd, int lane, const d4 &acc)
+{
+    const int c = lane & 15, g = lane >> 4;
+    const double af = pd[g == 0 ? 16 * HI + c : (g == 1 ? 32 + 16 * HI + c : 31)];
+    const double bf = pd[g == 0 ? 32 + 16 * HJ + c : (g == 1 ? 16 * HJ + c : 31)];
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc, 0, 0, 0);
 }
 // acc[r] of lane (c, g) = EE(16 HI + g + 4 r, 16 HJ + c); an off-diagonal tile in both orientations
 template <int K, int HI, int HJ>
@@ -529,26 +587,19 @@ __device__ __forceinline__ void fast_rebuild_col(const double *Lt, const double 
     }
 }
 
-// ... + p d0^T + d0 p^T (one k-step: A = [p, d0], B = [d0, p]) and out: the mirror triangle straight from the accumulators,
-// the lower triangle of the off-diagonal tiles through a private 16 x 17 transpose buffer.
-// Before either store every element takes its share of the even-part product, P+(t, s) += EE(rho(t), rho(s)) (vector rows and
-// columns read an exact zero): both orientations carry the same sum.
+// Out: the mirror triangle straight from the accumulators, the lower triangle of the off-diagonal tiles through a private
+// 16 x 17 transpose buffer.
+// Before either store every element takes its share of the even-part product and the rank-2 term (fast_ee_rank2),
+// P+(t, s) += EE(rho(t), rho(s)) (vector rows and columns read an exact zero): both orientations carry the same sum.
 template <int K, int J>
-__device__ __forceinline__ void fast_store_col(const double *pd, const double *ee, double *bufs, double *oP, int lane,
-                                               d4 (&acc)[FastShape<K>::NT], bool lower_only)
+__device__ __forceinline__ void fast_store_col(const double *ee, double *bufs, double *oP, int lane, d4 (&acc)[FastShape<K>::NT],
+                                               bool lower_only)
 {
     using F = FastShape<K>;
     constexpr int NT = F::NT, N = F::N, EES = FastEE<K>::EES, PAD = FastEE<K>::PAD;
     const int c = lane & 15, g = lane >> 4;
     {
         const int rj = fast_rho<N>(16 * J + c);
-        const double bf = pd[g == 0 ? 32 + rj : (g == 1 ? rj : 31)];
-#pragma unroll
-        for (int I = J; I < NT; ++I) {
-            const int ri = fast_rho<N>(16 * I + c);
-            const double af = pd[g == 0 ? ri : (g == 1 ? 32 + ri : 31)];
-            acc[I - J] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[I - J], 0, 0, 0);
-        }
         const double *eec = ee + (rj & PAD);                     // (31 & PAD = PAD)
 #pragma unroll
         for (int I = J; I < NT; ++I) {
@@ -1105,12 +1156,12 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         if (wave == 2) eacc = fast_ee_tile<K, 1, 0>(Et, lane);
         else if (wave == 3) eacc = fast_ee_tile<K, 1, 1>(Et, lane);
     }
-    __syncthreads();                                             // E^ is dead
+    __syncthreads();                                             // E^ is dead; p and the corrected d0 are complete
     double *ee = U;
-    if (wave == 0) fast_ee_publish<K, 0, 0>(ee, lane, eacc);
+    if (wave == 0) fast_ee_publish<K, 0, 0>(ee, lane, fast_ee_rank2<0, 0>(pd, lane, eacc));
     else if constexpr (EE::NTE > 1) {
-        if (wave == 2) fast_ee_publish<K, 1, 0>(ee, lane, eacc);
-        else if (wave == 3) fast_ee_publish<K, 1, 1>(ee, lane, eacc);
+        if (wave == 2) fast_ee_publish<K, 1, 0>(ee, lane, fast_ee_rank2<1, 0>(pd, lane, eacc));
+        else if (wave == 3) fast_ee_publish<K, 1, 1>(ee, lane, fast_ee_rank2<1, 1>(pd, lane, eacc));
     }
     d4 acc[NT];
 #pragma unroll
@@ -1119,12 +1170,12 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     else if (wave == 1) fast_rebuild_col<K, 1>(Lt, str, lane, acc);
     else if (wave == 2) fast_rebuild_col<K, 2>(Lt, str, lane, acc);
     else if constexpr (NT > 3) fast_rebuild_col<K, 3>(Lt, str, lane, acc);
-    __syncthreads();                                             // the factor is dead; p and EE are complete
+    __syncthreads();                                             // the factor is dead; EE is complete
     SLK_FSTAMP(14);
-    if (wave == 0) fast_store_col<K, 0>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
-    else if (wave == 1) fast_store_col<K, 1>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
-    else if (wave == 2) fast_store_col<K, 2>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
-    else if constexpr (NT > 3) fast_store_col<K, 3>(pd, ee, Lt, oP, lane, acc, a.lower_only != 0);
+    if (wave == 0) fast_store_col<K, 0>(ee, Lt, oP, lane, acc, a.lower_only != 0);
+    else if (wave == 1) fast_store_col<K, 1>(ee, Lt, oP, lane, acc, a.lower_only != 0);
+    else if (wave == 2) fast_store_col<K, 2>(ee, Lt, oP, lane, acc, a.lower_only != 0);
+    else if constexpr (NT > 3) fast_store_col<K, 3>(ee, Lt, oP, lane, acc, a.lower_only != 0);
     SLK_STAMP_NR(15);
     return true;
 }
