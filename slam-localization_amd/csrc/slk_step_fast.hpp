@@ -274,17 +274,64 @@ __device__ __forceinline__ bool so3_log_tab(const double *T, const Quat (&q)[NV]
     return true;
 }
 
-// exclusive prefix sums over the lanes (columns) of the entries E0 .. E0 + CNT - 1 of the packed lower triangle of a a^T
-template <int E0, int CNT>
-__device__ __forceinline__ void fast_scan_entries(const double (&av)[8], double (&G)[20])
+// The factor update needs, for every column j, 4 G_j = sum_{k < j} dZ_k dZ_k^T (8 x 8 symmetric; ldm_prefix of slk_kernels.hpp
+// takes the 36 entries from 36 wave scans).  Here in BLOCKS of four columns, block b = columns 4 b .. 4 b + 3:
+//   * fast_prefix_blocks: one wave runs acc <- mfma(fr, fr, acc) over the k-steps, fr = rows (c16 & 7) of dZ at column
+//     4 s + g (rows / columns 8 .. 15 of the tile repeat 0 .. 7 and are never read): after step s the top-left 8 x 8 of acc is
+//     the BASE 4 G_{4 (s + 1)} of block s + 1.  Lane (c16, g) holds rows g and g + 4 of column c16, and the lanes c16 >= 8
+//     the same numbers as the lanes c16 - 8: the lower half of the lanes keeps row g, the upper half row g + 4 -- ONE double
+//     per step and lane, in registers (no LDS is free while S is formed) until fast_prefix_park puts them, one full-wave
+//     store per step, into NKS slots of an 8 x 8 each (slot 0 = zeros), kPrefixSlot doubles apart: the sixteen blocks of a
+//     wave's lanes then read sixteen different banks.
+//   * fast_prefix_tail: lane j = column j sums the outer products of the up-to-three columns before it INSIDE its block; a
+//     neighbour outside the block is replaced by column 63 of dZ, which is exactly zero for every N <= 60 (an integer
+//     select on the address, none on values).
+//   * lane j's 4 G_j = slot[min(j >> 2, NKS - 1)] + tail.  The clamp is the dead-lane rule: fast_ldm_columns tests d > 0 over
+//     all 64 lanes, so lanes j >= N need a T_j that is positive definite -- theirs is that of a live column (columns >= N of dZ
+//     are zero: a dead lane inside the last block has the true prefix, one beyond it G of that block's first column).
+// The factor 1/4 (a = 1/2 dZ) is a power of two and goes into T = S - 1/4 (4 G) of fast_ldm_columns, exactly.
+// All of it runs on the wave that consumes it (wave 3; chain and tails beside S, where that wave was idle): the slots are
+// written and read by one wave, and the step has one barrier less than with the sums handed over from another wave.
+constexpr int kPrefixSlot = 66;
+template <int NKS>
+__device__ __forceinline__ void fast_prefix_blocks(const double *dZi, int c16, int g4, double (&Gs)[NKS - 1])
 {
+    static_assert(NKS * kPrefixSlot <= 1088, "block bases: the dead Yp rows");
+    const double *fp = dZi + ((c16 & 7) >> 1) * 128 + 2 * g4 + (c16 & 1);
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int e = 0; e < CNT; ++e) {
-        constexpr int dummy = 0; (void)dummy;
-        const int q = E0 + e;
-        const int r = (q >= 1) + (q >= 3) + (q >= 6) + (q >= 10) + (q >= 15) + (q >= 21) + (q >= 28), cc = q - r * (r + 1) / 2;
-        const double pr = av[r] * av[cc];
-        G[e] = wave_inclusive_scan(pr) - pr;
+    for (int s = 0; s < NKS - 1; ++s) {
+        const double fr = fp[8 * s];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr, fr, acc, 0, 0, 0);
+        Gs[s] = (c16 < 8) ? acc[0] : acc[1];
+    }
+}
+template <int NKS>
+__device__ __forceinline__ void fast_prefix_park(double *slots, int c16, int g4, const double (&Gs)[NKS - 1])
+{
+    double *sp = slots + 8 * (c16 & 7) + g4 + 4 * (c16 >> 3);
+    sp[0] = 0.0;
+#pragma unroll
+    for (int s = 0; s < NKS - 1; ++s) sp[(s + 1) * kPrefixSlot] = Gs[s];
+}
+__device__ __forceinline__ void fast_prefix_tail(const double *dZi, int lane, double (&Gs)[36])
+{
+    const double2 *dz2 = reinterpret_cast<const double2 *>(dZi);
+    const int q = lane & 3;
+#pragma unroll
+    for (int n = 1; n <= 3; ++n) {
+        const int cn = (q >= n) ? lane - n : 63;
+        double v[8];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { const double2 t = dz2[p * 64 + cn]; v[2 * p] = t.x; v[2 * p + 1] = t.y; }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+#pragma unroll
+            for (int cc = 0; cc <= r; ++cc) {
+                const int e = r * (r + 1) / 2 + cc;
+                Gs[e] = (n == 1) ? v[r] * v[cc] : fma(v[r], v[cc], Gs[e]);
+            }
+        }
     }
 }
 
@@ -318,11 +365,12 @@ template <int K> struct FastPairTableHolder { static __device__ const FastPairTa
 template <int K> __device__ const FastPairTable<K> FastPairTableHolder<K>::tab = FastPairTable<K>();
 
 // ldm_columns (slk_kernels.hpp) with the column's deviations a_j = 1/2 dZ_j fetched from LDS where they are used instead of
-// held in sixteen registers beside the 36 prefix sums: lane j = column j, Gf = prefix sums, Sm = S (8 x 8), kept = rows
-// that survived the gate.  Writes Wb[bw_idx(j, :)] = 1/2 w~_j and mdiag[j] = sqrt(d_j); false if Pk - K S K^T is not
+// held in sixteen registers beside the 36 prefix sums: lane j = column j, Gf + bp[8 c + r] = 4 G_j = the prefix sums of
+// dZ dZ^T (tail + the 8 x 8 base of the lane's block, see fast_prefix_blocks; the base is fetched and the 1/4 applied where
+// column c of T_j = S - G_j is formed: all 36 bases fetched ahead spill), Sm = S (8 x 8), kept = rows that survived the gate.  Writes Wb[bw_idx(j, :)] = 1/2 w~_j and mdiag[j] = sqrt(d_j); false if Pk - K S K^T is not
 // positive definite.
 #define SLK_G(r, c) Gf[(r) * ((r) + 1) / 2 + (c)]
-__device__ __forceinline__ bool fast_ldm_columns(double (&Gf)[36], const double *dZi, const double *Sm, unsigned kept, int lane, int N,
+__device__ __forceinline__ bool fast_ldm_columns(double (&Gf)[36], const double *bp, const double *dZi, const double *Sm, unsigned kept, int lane, int N,
                                                  double *Wb, double *mdiag)
 {
     const bool live = lane < N;
@@ -338,14 +386,14 @@ __device__ __forceinline__ bool fast_ldm_columns(double (&Gf)[36], const double 
     for (int j = 0; j < 8; ++j) {
         if (full) {
 #pragma unroll
-            for (int r = j; r < 8; ++r) SLK_G(r, j) = Sm[r + 8 * j] - SLK_G(r, j);
+            for (int r = j; r < 8; ++r) SLK_G(r, j) = fma(-0.25, bp[8 * j + r] + SLK_G(r, j), Sm[r + 8 * j]);
         } else {
             const bool kj = (kept >> j) & 1u;
 #pragma unroll
             for (int r = j; r < 8; ++r) {
                 const bool in = kj && ((kept >> r) & 1u);
                 const double sv = Sm[in ? r + 8 * j : 0];
-                SLK_G(r, j) = in ? sv - SLK_G(r, j) : ((r == j) ? 1.0 : 0.0);
+                SLK_G(r, j) = in ? fma(-0.25, bp[8 * j + r] + SLK_G(r, j), sv) : ((r == j) ? 1.0 : 0.0);
             }
         }
         double d = SLK_G(j, j);
@@ -776,7 +824,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     SLK_FSTAMP(4);
 
     // ---- phase 2: S = 1/2 sum (Z_i - mean_z)(Z_i - mean_z)^T + R (:238) on wave 1
-    double Gs[20];
+    double Gs[NKS - 1], Gt[36];                                 // wave 3: the factor update's prefix sums, block bases and tails
     if (wave == 1) {
         d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -790,18 +838,24 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         const double *R = a.R + (size_t)bidx * a.r_stride;
         const int row = lane & 7, col = lane >> 3;
         Sm[lane] = 0.5 * ((tmpS[lane] + tmpS[64 + lane]) - (double)S * dz0[row] * dz0[col]) + R[lane];
-    } else if (wave >= 2) {
-        // prefix sums over the columns of a a^T (ldm_prefix: the 36 entries of the packed lower triangle, lane = column),
-        // the first 16 by wave 2, the others by wave 3: one wave's 36 scans were the longest serial stretch of the step
-        double av[8];
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) av[cc] = 0.5 * dZi[(cc >> 1) * 128 + 2 * lane + (cc & 1)];
-        if (wave == 2) fast_scan_entries<0, 16>(av, Gs);
-        else fast_scan_entries<16, 20>(av, Gs);
-        SLK_WSTAMP(3, 21);
+    } else if (wave == 3) {
+        // prefix sums over the columns of dZ dZ^T for the factor update (fast_prefix_blocks): the base of every block of four
+        // columns from an MFMA chain beside S's, kept in registers -- no LDS is free before S is done.  On the wave that
+        // consumes them: its hand-over through LDS below needs no barrier.
+        fast_prefix_tail(dZi, lane, Gt);                        // each column's sum inside its block
+        __builtin_amdgcn_sched_barrier(0);                      // (tails, then the chain: the neighbours' deviations are dead by then)
+        fast_prefix_blocks<NKS>(dZi, c16, g4, Gs);              // (no stamp here: with one the stamps build spills 42 registers)
     }
     __syncthreads();
     SLK_FSTAMP(6);
+    // The block bases go to the Yp rows (dead: S is done), [0, NKS * kPrefixSlot) of the union, from the MFMA layout to lane =
+    // column: wave 3 alone writes and reads them, no barrier.  Ahead of the gate: their registers are free across it.  Wb
+    // aliases [0, 512): every base is read before fast_ldm_columns' first Wb store (the stores are its last step, behind the
+    // last column of T).
+    if (wave == 3) {
+        fast_prefix_park<NKS>(Yp, c16, g4, Gs);
+        wave_sync();
+    }
 
     // ---- gate: removeOutliers (:723-754) with the shifted second erase (:741-744); every wave takes the same decisions
     unsigned kept = 0xffu, nout = 0u;
@@ -845,11 +899,6 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
 
     // ---- gain side.  wave 3: columns of the factor update.  wave 0: x = S^-1 nu over the surviving rows (rejected rows
     // as identity rows), b = 1/2 dZ x, delta = K nu = L b (:257, :263), then the reference point of the mean loop.
-    if (wave == 2) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Yp[e * 64 + lane] = Gs[e];        // (the Yp rows are dead: S is done)
-    }
-    __syncthreads();
     if (wave == 0) {
         double gg[8][8], gi[8], y[8];
         // (set-up with every row kept -- kept is wave-uniform and nearly always 0xff -- without the selects; one chain for both.
@@ -943,12 +992,9 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     }
     else if (wave == 3) {
         SLK_WSTAMP(3, 22);
-        double Gf[36];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Gf[e] = Yp[e * 64 + lane];
-#pragma unroll
-        for (int e = 16; e < 36; ++e) Gf[e] = Gs[e - 16];
-        const bool pdok = fast_ldm_columns(Gf, dZi, Sm, kept, lane, N, Wb, mdiag);
+        const int blk = lane >> 2;
+        const double *bp = Yp + (blk < NKS - 1 ? blk : NKS - 1) * kPrefixSlot;           // (dead lanes: the last live block)
+        const bool pdok = fast_ldm_columns(Gt, bp, dZi, Sm, kept, lane, N, Wb, mdiag);
         if (!pdok && lane == 0) ints[48] = 1;
         SLK_WSTAMP(3, 23);
     }
