@@ -38,6 +38,20 @@
 
 namespace slk {
 
+// f(FastIdx<I>()) for I = B .. E - 1 while I <= last (wave-uniform, in a scalar register): nested ifs, one scalar compare
+// and branch per step, every step its own straight-line code with compile-time indices.  (A `break` in an unrolled loop
+// becomes a run-time trip count, the loop stays rolled and its register arrays are indexed at run time.)
+template <int I> struct FastIdx { static constexpr int value = I; };
+template <int B, int E, class F> __device__ __forceinline__ void fast_steps_to(int last, F &&f)
+{
+    if constexpr (B < E) {
+        if (B <= last) {
+            f(FastIdx<B>());
+            fast_steps_to<B + 1, E>(last, f);
+        }
+    }
+}
+
 template <int K> struct FastShape {
     static constexpr int N = 12 + 6 * K, Nq = 13 + 7 * K, S = 2 * N + 1, NSO3 = K + 1;
     static constexpr int NT = (N + 15) / 16, NTL = NT * (NT + 1) / 2, NKS = (N + 3) / 4;
@@ -289,6 +303,11 @@ __device__ __forceinline__ bool so3_log_tab(const double *T, const Quat (&q)[NV]
 //   * lane j's 4 G_j = slot[min(j >> 2, NKS - 1)] + tail.  The clamp is the dead-lane rule: fast_ldm_columns tests d > 0 over
 //     all 64 lanes, so lanes j >= N need a T_j that is positive definite -- theirs is that of a live column (columns >= N of dZ
 //     are zero: a dead lane inside the last block has the true prefix, one beyond it G of that block's first column).
+//   * the columns beyond jmax (the last one a measurement row depends on) of dZ are exact zeros: the steps of the chain
+//     beyond ksmax = jmax >> 2 add +0 and leave the sum over all live columns, bit for bit, in every later base.  So only
+//     min(ksmax + 2, NKS) slots are parked and the slot index is clamped to ksmax + 1 as well (fast_prefix_slot): every
+//     block behind the last live one reads that sum from the first slot that holds it.  (The chain itself runs all its
+//     steps, see there.)
 // The factor 1/4 (a = 1/2 dZ) is a power of two and goes into T = S - 1/4 (4 G) of fast_ldm_columns, exactly.
 // All of it runs on the wave that consumes it (wave 3; chain and tails beside S, where that wave was idle): the slots are
 // written and read by one wave, and the step has one barrier less than with the sums handed over from another wave.
@@ -299,6 +318,9 @@ __device__ __forceinline__ void fast_prefix_blocks(const double *dZi, int c16, i
     static_assert(NKS * kPrefixSlot <= 1088, "block bases: the dead Yp rows");
     const double *fp = dZi + ((c16 & 7) >> 1) * 128 + 2 * g4 + (c16 & 1);
     d4 acc = {0.0, 0.0, 0.0, 0.0};
+    // (all NKS - 1 steps, also those beyond the last live one that add exact zeros: with a uniform exit per step, or per two
+    // steps, the chain is no longer one block, the operand fetch and its address stay live beside the 36 tails and the 14
+    // bases, and the k = 8 kernel spills 8 to 12 registers)
 #pragma unroll
     for (int s = 0; s < NKS - 1; ++s) {
         const double fr = fp[8 * s];
@@ -307,12 +329,21 @@ __device__ __forceinline__ void fast_prefix_blocks(const double *dZi, int c16, i
     }
 }
 template <int NKS>
-__device__ __forceinline__ void fast_prefix_park(double *slots, int c16, int g4, const double (&Gs)[NKS - 1])
+__device__ __forceinline__ void fast_prefix_park(double *slots, int c16, int g4, int ksmax, const double (&Gs)[NKS - 1])
 {
     double *sp = slots + 8 * (c16 & 7) + g4 + 4 * (c16 >> 3);
     sp[0] = 0.0;
-#pragma unroll
-    for (int s = 0; s < NKS - 1; ++s) sp[(s + 1) * kPrefixSlot] = Gs[s];
+    fast_steps_to<0, NKS - 1>(ksmax, [&](auto ix) __attribute__((always_inline)) {
+        constexpr int s = decltype(ix)::value;
+        sp[(s + 1) * kPrefixSlot] = Gs[s];
+    });
+}
+// the slot of lane j's block: its own up to the one behind the last live k-step, whose base is the sum over every live column
+__device__ __forceinline__ int fast_prefix_slot(int j, int ksmax, int nks)
+{
+    const int last = ksmax + 1 < nks - 1 ? ksmax + 1 : nks - 1;
+    const int blk = j >> 2;
+    return blk < last ? blk : last;
 }
 __device__ __forceinline__ void fast_prefix_tail(const double *dZi, int lane, double (&Gs)[36])
 {
@@ -446,6 +477,10 @@ __device__ __forceinline__ bool fast_ldm_columns(double (&Gf)[36], const double 
 //            JB = 1: 16 / 20 / 14 / 0                                    JB = 0: 10 / 10 / 0 / 0
 //   NT = 3   wave 0: (1,0) (0,0)   wave 1: (2,1) (1,1)   wave 2: (2,0)   wave 3: (2,2)
 //            JB = 2: 16 / 16 / 18 / 6 = 56 (18 / 18 / 18 / 6)            JB = 1: 16 / 10 / 12 / 0     JB = 0: 10 / 0 / 6 / 0
+// These are the counts with jmax (the last column a measurement row depends on) at the end of tile column JB, for which the
+// map is chosen.  Below the diagonal the k-steps of M(Kb, J) beyond jmax are dropped as well (fast_ldm_wave_tiles): at
+// jmax = 35 (the benchmark: tile row 2 has one live k-step of four) NT = 4 runs 19 / 23 / 18 / 10 = 70, NT = 3 (k = 5, 6)
+// 16 / 13 / 15 / 6 = 50.
 template <int NT> __host__ __device__ constexpr int fast_ldm_wave(int I, int J)
 {
     if (NT == 4) return J == 0 ? ((I == 3 || I == 0) ? 0 : 1) : (J == 1 ? 2 : 3);
@@ -471,11 +506,15 @@ template <int NT> __host__ __device__ constexpr bool fast_ldm_owns(int W, int J,
 }
 
 // the tiles of wave W: every M(Kb, J) once, then into each of the wave's tiles (I, J), I >= Kb -- per output element the
-// operations and their order (Kb ascending from J) of one tile at a time
+// operations and their order (Kb ascending from J) of one tile at a time.  Below the diagonal (Kb > J) the rows k > jmax of
+// M(Kb, J) are a_k w~^T = 0 exactly, so the product with L(I, Kb) runs its k-steps (four rows each) only while
+// 16 Kb + 4 s <= jmax, a uniform exit, and fetches only those fragments of L; a diagonal tile keeps all four (its rows
+// beyond jmax are identity rows, which copy L's columns).
 template <int NT, int W, int MAXT>
 __device__ __forceinline__ void fast_ldm_wave_tiles(const double *Lt, const double *dZi, const double *Wb, const double *mdiag, int lane,
-                                                    int JB, d4 (&acc)[MAXT])
+                                                    int jmax, d4 (&acc)[MAXT])
 {
+    const int JB = jmax >> 4;
     const int c = lane & 15, g = lane >> 4;
     const int lw = (g >> 1) * 128 + 2 * c + (g & 1);           // lane part of bw_idx(16 X + c, g)
 #pragma unroll
@@ -485,6 +524,7 @@ __device__ __forceinline__ void fast_ldm_wave_tiles(const double *Lt, const doub
 #pragma unroll
         for (int Kb = J; Kb < NT; ++Kb) {
             if (!fast_ldm_owns<NT>(W, J, Kb) || Kb > JB) continue;
+            const int slast = (Kb > J) ? (jmax - 16 * Kb) >> 2 : 3;   // the last k-step of M(Kb, J) with a row <= jmax (Kb <= JB: >= 0)
             d4 mt = {0.0, 0.0, 0.0, 0.0};
             const double a0 = dZi[32 * Kb + lw], a1 = dZi[256 + 32 * Kb + lw];
             mt = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, wf0, mt, 0, 0, 0);
@@ -501,31 +541,38 @@ __device__ __forceinline__ void fast_ldm_wave_tiles(const double *Lt, const doub
             for (int I = Kb; I < NT; ++I) {
                 if (fast_ldm_wave<NT>(I, J) != W) continue;
                 double lf[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) lf[s] = Lt[(I * (I + 1) / 2 + Kb) * 256 + 64 * s + lane];
+                const double *lp = Lt + (I * (I + 1) / 2 + Kb) * 256 + lane;
+                fast_steps_to<0, 4>(slast, [&](auto ix) __attribute__((always_inline)) {
+                    constexpr int s = decltype(ix)::value;
+                    lf[s] = lp[64 * s];
+                });
                 d4 &a = acc[fast_ldm_slot<NT>(I, J)];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) a = __builtin_amdgcn_mfma_f64_16x16x4f64(mt[s], lf[s], a, 0, 0, 0);
+                fast_steps_to<0, 4>(slast, [&](auto ix) __attribute__((always_inline)) {
+                    constexpr int s = decltype(ix)::value;
+                    a = __builtin_amdgcn_mfma_f64_16x16x4f64(mt[s], lf[s], a, 0, 0, 0);
+                });
             }
         }
     }
 }
 
-// L <- L M on the matrix cores, tiled factor (see ldm_product in slk_kernels.hpp for the algebra).  JB = tile column of the
-// last column any measurement row depends on: beyond it M is the identity (dZ rows are exactly zero), those blocks are
-// skipped.  fill() runs between the two barriers (everything but the factor is dead there).
+// L <- L M on the matrix cores, tiled factor (see ldm_product in slk_kernels.hpp for the algebra).  jmax = the last column
+// any measurement row depends on, JB = its tile column: beyond it M is the identity (dZ rows are exactly zero), those blocks
+// are skipped, and so are the k-steps beyond jmax below the diagonal (fast_ldm_wave_tiles).  fill() runs between the two
+// barriers (everything but the factor is dead there).
 template <int NT, class FillFn>
 __device__ __forceinline__ void ldm_product_tiled(double *Lt, const double *dZi, const double *Wb, const double *mdiag, int lane,
-                                                  int wave, int JB, FillFn fill)
+                                                  int wave, int jmax, FillFn fill)
 {
     constexpr int MAXT = (NT == 4) ? 3 : 2;
+    const int JB = jmax >> 4;
     d4 acc[MAXT];
 #pragma unroll
     for (int q = 0; q < MAXT; ++q) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
-    if (wave == 0) fast_ldm_wave_tiles<NT, 0>(Lt, dZi, Wb, mdiag, lane, JB, acc);
-    else if (wave == 1) fast_ldm_wave_tiles<NT, 1>(Lt, dZi, Wb, mdiag, lane, JB, acc);
-    else if (wave == 2) fast_ldm_wave_tiles<NT, 2>(Lt, dZi, Wb, mdiag, lane, JB, acc);
-    else fast_ldm_wave_tiles<NT, 3>(Lt, dZi, Wb, mdiag, lane, JB, acc);
+    if (wave == 0) fast_ldm_wave_tiles<NT, 0>(Lt, dZi, Wb, mdiag, lane, jmax, acc);
+    else if (wave == 1) fast_ldm_wave_tiles<NT, 1>(Lt, dZi, Wb, mdiag, lane, jmax, acc);
+    else if (wave == 2) fast_ldm_wave_tiles<NT, 2>(Lt, dZi, Wb, mdiag, lane, jmax, acc);
+    else fast_ldm_wave_tiles<NT, 3>(Lt, dZi, Wb, mdiag, lane, jmax, acc);
     __syncthreads();                                  // every wave has read what it needs of the old factor
 #pragma unroll
     for (int I = 0; I < NT; ++I)
@@ -706,7 +753,11 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     // ---- phase 0: mean, tiled factor, small arrays.  Every global load is issued before the first use; the conditions that
     // hand the filter to the general body -- failed first factorisation, pose index out of range (SLK_ST_BAD_INDEX there),
     // a rotation column that may exceed pi (Msckf.hpp:407-413: covXZ = L A would not hold) -- meet in one barrier
-    int jmax = 0, bad;
+    // jmax = the last column any measurement row depends on (a feature on pose c reaches the columns j <= tp + 5: the lanes
+    // beyond evaluate X_0, y+ = y- = 0 and dZ_j = 0 exactly), ksmax = jmax >> 2 = the last k-step (four columns) with a live
+    // column, both wave-uniform and held in scalar registers.  S, the block bases of the prefix sums, delta = L b and the
+    // k-blocks below the diagonal of the factor update stop there: what lies beyond multiplies exact zeros.
+    int jmax = 0, ksmax, bad;
     // the factor: from msckf_chol_kernel's workspace, or (a.wsfail == nullptr) factored HERE by wave 0 -- cholp_factor, panel
     // by rows, straight into the tiles -- while the other waves fetch the small arrays (against the factor through the
     // workspace for every step: same step time, 0.74 x instead of 1.28 x the algorithmic bytes,
@@ -738,6 +789,8 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             const int cp = ok ? (int)cf : 0, tp = cp ? 6 + 6 * cp : 0;
             jmax = (tp + 5 > jmax) ? tp + 5 : jmax;
         }
+        jmax = __builtin_amdgcn_readfirstlane(jmax);
+        ksmax = jmax >> 2;
         bad |= !ok;
         if (tid < NSO3) bad |= !(pdg < 9.869604401089358);
         if (tid < Nq) mu[tid] = mu0;
@@ -827,11 +880,11 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     double Gs[NKS - 1], Gt[36];                                 // wave 3: the factor update's prefix sums, block bases and tails
     if (wave == 1) {
         d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
+        fast_steps_to<0, NKS>(ksmax, [&](auto ix) __attribute__((always_inline)) {      // (the columns beyond jmax hold y+ = y- = 0)
+            constexpr int ks = decltype(ix)::value;
             const double fr = Yp[ks * 68 + g4 * 17 + c16];      // rows [y+ ; y-] of column 4 ks + g
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr, fr, acc, 0, 0, 0);
-        }
+        });
         if (c16 < 8) { tmpS[g4 + 8 * c16] = acc[0]; tmpS[g4 + 4 + 8 * c16] = acc[1]; }
         else { tmpS[64 + g4 + 8 * (c16 - 8)] = acc[2]; tmpS[64 + g4 + 4 + 8 * (c16 - 8)] = acc[3]; }
         wave_sync();
@@ -848,12 +901,12 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     }
     __syncthreads();
     SLK_FSTAMP(6);
-    // The block bases go to the Yp rows (dead: S is done), [0, NKS * kPrefixSlot) of the union, from the MFMA layout to lane =
-    // column: wave 3 alone writes and reads them, no barrier.  Ahead of the gate: their registers are free across it.  Wb
-    // aliases [0, 512): every base is read before fast_ldm_columns' first Wb store (the stores are its last step, behind the
-    // last column of T).
+    // The block bases go to the Yp rows (dead: S is done), the first min(ksmax + 2, NKS) slots of [0, NKS * kPrefixSlot) of the
+    // union (the slots behind them are neither written nor read), from the MFMA layout to lane = column: wave 3 alone writes
+    // and reads them, no barrier.  Ahead of the gate: their registers are free across it.  Wb aliases [0, 512): every base is
+    // read before fast_ldm_columns' first Wb store (the stores are its last step, behind the last column of T).
     if (wave == 3) {
-        fast_prefix_park<NKS>(Yp, c16, g4, Gs);
+        fast_prefix_park<NKS>(Yp, c16, g4, ksmax, Gs);
         wave_sync();
     }
 
@@ -961,15 +1014,17 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             const double *Lrow = Lt + (It * (It + 1) / 2) * 256 + (t & 15);
             double part[NT];
 #pragma unroll
-            for (int Jb = 0; Jb < NT; ++Jb) {
-                double s = 0.0;
+            for (int Jb = 0; Jb < NT; ++Jb) part[Jb] = 0.0;
+            // groups of eight columns up to the one that holds jmax: b_j = 0 beyond it, the sums stay what they are
+            fast_steps_to<0, 2 * NT>(jmax >> 3, [&](auto ix) __attribute__((always_inline)) {
+                constexpr int Jb = decltype(ix)::value >> 1, j0 = 8 * (decltype(ix)::value & 1);
+                double s = part[Jb];
 #pragma unroll
-                for (int jj = 0; jj < 16; ++jj) {
+                for (int jj = j0; jj < j0 + 8; ++jj)
                     if (16 * Jb + jj < N) s = fma(Lrow[Jb * 256 + jj * 16], bvec[16 * Jb + jj], s);
-                    if ((jj & 7) == 7) __builtin_amdgcn_sched_barrier(0);   // (eight columns of loads in flight at a time: registers)
-                }
                 part[Jb] = s;
-            }
+                __builtin_amdgcn_sched_barrier(0);               // (eight columns of loads in flight at a time: registers)
+            });
             double dl = part[0];
 #pragma unroll
             for (int Jb = 1; Jb < NT; ++Jb) dl += (It >= Jb) ? part[Jb] : 0.0;      // (tile columns right of the row's own hold other tiles)
@@ -992,8 +1047,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     }
     else if (wave == 3) {
         SLK_WSTAMP(3, 22);
-        const int blk = lane >> 2;
-        const double *bp = Yp + (blk < NKS - 1 ? blk : NKS - 1) * kPrefixSlot;           // (dead lanes: the last live block)
+        const double *bp = Yp + fast_prefix_slot(lane, ksmax, NKS) * kPrefixSlot;       // (dead lanes: the last live block)
         const bool pdok = fast_ldm_columns(Gt, bp, dZi, Sm, kept, lane, N, Wb, mdiag);
         if (!pdok && lane == 0) ints[48] = 1;
         SLK_WSTAMP(3, 23);
@@ -1004,7 +1058,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
 
     // ---- applyDelta's factor: L' = L chol(I - B B^T) (:262-263, :659-662)
     unsigned long long pt0 = 0, pt1 = 0;                       // pair descriptors of the mean loop
-    ldm_product_tiled<NT>(Lt, dZi, Wb, mdiag, lane, wave, jmax >> 4, [&]() {
+    ldm_product_tiled<NT>(Lt, dZi, Wb, mdiag, lane, wave, jmax, [&]() {
         pt0 = FastPairTableHolder<K>::tab.v[tid < NP ? tid : 0];
         pt1 = FastPairTableHolder<K>::tab.v[(wave == 1 && 256 + lane < NP) ? 256 + lane : 0];
         for (int e = tid; e < NKS * 128; e += 256) Et[e] = 0.0;
