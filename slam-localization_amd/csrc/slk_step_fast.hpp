@@ -794,8 +794,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         bad |= !ok;
         if (tid < NSO3) bad |= !(pdg < 9.869604401089358);
         if (tid < Nq) mu[tid] = mu0;
-        if (tid < 64) { str[tid] = 0.0; pd[tid] = 0.0; ints[tid] = 0; }
-        if (tid < 32) { d0[tid] = 0.0; md32[tid] = 0.0; }
+        if (tid < 64) ints[tid] = 0;                    // (str, pd, d0, md32: behind phase 1 -- the factorisation's colbuf lies on them)
         if (tid < 26) T[tid] = tabv;
         if (!here) {
 #pragma unroll
@@ -817,16 +816,44 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
                 for (int e = tid - 64; e < CholM<NT>::NTL * 128; e += NTHREADS - 64) Lt2[e] = double2{0.0, 0.0};   // (every wave but wave 0)
             }
             __syncthreads();
-            if (wave == 0) bad |= cholp_factor<NT, 2, N>(fa, Lt, N, U, lane) >= 0;   // (the union region is free until phase 1: its colbuf)
+            // RELEASE: h(X) of a feature on pose c reads the rows tp .. tp + 5 of the factor at the columns j <= tp + 5 <= jmax,
+            // and step s of the factorisation leaves L(t, j) final for every j <= 4 s + 3.  Behind the tile stores of step ksmax
+            // (the step that holds column jmax; cp <= K, so it is one of the live steps 0 .. NKS - 1 and the barrier is always
+            // met) wave 0 meets the other three in one workgroup barrier and runs its remaining steps -- columns beyond jmax,
+            // which nothing reads before the barrier that closes phase 1 -- while they evaluate their features.  With the
+            // newest pose observed (ksmax = NKS - 1) the barrier stands at the end of the factorisation.
+            // colbuf = [oRef, oStr + 64): ref, delta, md32, d0, d0s, pd, cq, str -- all first written behind phase 1 (the union
+            // region, where it used to be, holds Yp, which the early h(X) writes)
+            static_assert(CholM<NT>::COLBUF <= F::oStr + 64 - F::oRef, "colbuf fits the arrays of the gain phase and the mean loop");
+            if (wave == 0) {
+                bad |= cholp_factor<NT, 2, N>(fa, Lt, N, ref, lane, ksmax, [&]() __attribute__((always_inline)) {
+                    wave_sync();                                // (the tile stores of this step and every one before it)
+                    __builtin_amdgcn_s_barrier();
+                    SLK_WSTAMP(0, 16);
+                }) >= 0;
+            } else {
+                __syncthreads();
+            }
+        } else {
+            __syncthreads();                                    // (the factor through the workspace: every wave stored its part of the tiles)
         }
     }
-    if (__syncthreads_or(bad)) SLK_FBAIL(2);
-    SLK_FSTAMP(3);
+    SLK_FSTAMP(3);                                              // (thread 0: the end of the factorisation)
 
-    // ---- phase 1: Z = h(X) (Msckf.hpp:231-232), one wave per feature, lane j = the sigma pair of column j
-    {
-        const int f = wave;
-        const int cp = (int)mp[4 * f + 3];
+    // ---- phase 1: Z = h(X) (Msckf.hpp:231-232), one wave per feature, lane j = the sigma pair of column j.  Waves 1 - 3 start
+    // behind the release above, wave 0 behind its last step; the filter may be one that is about to leave (failed
+    // factorisation, bad pose index, rotation bound -- decided in the barrier that closes this phase): the pose index is
+    // clamped before it forms an address, everything else h(X) reads lies at addresses that do not depend on data.
+    // Feature 0: with R = wave 0's steps behind the release and H = one h(X), wave 0 taking it ends the phase at R + H, wave 1
+    // taking it as a second pass at max(R, 2 H) -- ahead when R >= H.  H is about the time of three of the late steps
+    // (profiles/README.md), so the second pass runs when at least three steps follow the release (wave-uniform: ONE copy of
+    // the code, a uniform loop), else every wave has its own feature
+    const bool second = ksmax + 3 < NKS;
+    int f = wave;
+    for (bool go = wave != 0 || !second; go; go = second && f == 1, f = 0) {
+        if (f == wave) { SLK_WSTAMP(0, 17); SLK_WSTAMP(1, 19); }
+        const double cf = mp[4 * f + 3];
+        const int cp = (cf >= 0.0 && cf <= (double)K) ? (int)cf : 0;
         const int tp = cp ? 6 + 6 * cp : 0, sp = cp ? 6 + 7 * cp : 0;
         const double fx = mp[4 * f], fy = mp[4 * f + 1], fz = mp[4 * f + 2];
         const int j = lane, Jc = j >> 4;
@@ -871,9 +898,15 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             innov[2 * f + 1] = a.z[(size_t)bidx * 8 + 2 * f + 1] - (Z01 + e1);
             dz0[2 * f] = e0; dz0[2 * f + 1] = e1;
         }
+        SLK_WSTAMP(0, 18); SLK_WSTAMP(1, 21);
     }
-    __syncthreads();
+    // the barrier that closes phase 1 is the one in which the conditions of phase 0 meet: failed factorisation, bad index and
+    // rotation bound first, then the flag of h(X)'s exponential -- both before any global write
+    if (__syncthreads_or(bad)) SLK_FBAIL(2);
     if (ints[50]) SLK_FBAIL(3);
+    // (the factorisation's colbuf is dead: the zeros these arrays start from; their first readers are phases away)
+    if (tid < 64) { str[tid] = 0.0; pd[tid] = 0.0; }
+    if (tid < 32) { d0[tid] = 0.0; md32[tid] = 0.0; }
     SLK_FSTAMP(4);
 
     // ---- phase 2: S = 1/2 sum (Z_i - mean_z)(Z_i - mean_z)^T + R (:238) on wave 1

@@ -10,7 +10,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-STAMPS = [(0, "entry"), (3, "load + first factorisation (wave 0), mean, small arrays"), (4, "Z = h(X), zbar, innovation"), (6, "S (wave 0)"), (7, "gate"),
+STAMPS = [(0, "entry"), (3, "load + first factorisation (wave 0), mean, small arrays"), (4, "Z = h(X), zbar, innovation: wave 0's, behind its factorisation"), (6, "S (wave 0)"), (7, "gate"),
           (8, "x, b, delta (wave 0) | scan + columns (wave 3)"), (11, "factor update L M"), (12, "mean loop"),
           (13, "correction, odd / even split, mean out"), (14, "rebuild MFMA"), (15, "rank-2 + store")]
 
@@ -51,6 +51,15 @@ def main():
         m = lambda a, b: np.median(x[:, a] - x[:, b])
         print(f"  wave 3: at its columns {m(22, 7):.0f} after the gate; block bases + columns {m(23, 22):.0f}")
         print(f"  wave 0: x = S^-1 nu {m(24, 7):.0f} after the gate; b, delta = L b, reference {m(25, 24):.0f}; waits for wave 3 {m(8, 25):.0f}")
+    # early h(X): wave 0 releases the finished columns of the factor in the step that holds jmax (slot 16), waves 1 - 3 evaluate
+    # their features from there (wave 1: 19 .. 21), wave 0 behind its last step (17 .. 18; stamp 3 = the end of its factorisation)
+    if (x[:, 16] > 0).all() and (x[:, 21] > 0).all():
+        print(f"  wave 0: releases the factor {m(16, 0):.0f} after entry, {m(3, 16):.0f} before its factorisation ends")
+        print(f"  wave 1: h(X) starts {m(19, 16):.0f} after the release, takes {m(21, 19):.0f}, is done {m(3, 21):.0f} before wave 0's factorisation ends")
+        if (x[:, 18] > 0).all():
+            print(f"  wave 0: h(X) starts {m(17, 3):.0f} after its factorisation, takes {m(18, 17):.0f}; the closing barrier {m(4, 18):.0f}")
+        else:
+            print(f"  wave 0: no feature of its own; the closing barrier {m(4, 3):.0f} after its factorisation")
     # which waves left the direct SO(3) series in the first mean-loop pass (bit 0 exp, bit 1 log; wave 1: bits 2 / 3 = its second round)
     for w, slot in enumerate((26, 27, 29, 30)):
         print(f"  mean loop, wave {w}: angle-halving exp / log codes {np.bincount(x[:, slot].astype(int), minlength=4)}")
