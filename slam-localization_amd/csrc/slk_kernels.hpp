@@ -689,15 +689,17 @@ __device__ __forceinline__ void lds_store4_lane_ranges(unsigned addr, const doub
 // (slk_step_fast.hpp: tile (I, J) at (I (I + 1) / 2 + J) * 256, element (t, j) at (j & 15) * 16 + (t & 15), exact zeros above the
 // diagonal and in the padding), LDS
 // The tile variant can RELEASE the columns it has finished to the other waves of the workgroup while it goes on: behind the
-// tile stores of step ksync (k0 = 4 ksync; wave-uniform, one scalar compare and branch per step, every step straight-line code)
-// it calls rel() once -- the caller's workgroup barrier.  After it L(t, j) is final for every j <= 4 ksync + 3; the later steps
-// store columns beyond that only.  ksync must be the index of a live step (0 .. (NC - 1) / 4), or rel() never runs.
+// tile stores of every step s whose bit is set in relmask (k0 = 4 s; a wave-uniform mask in one scalar register, tested with the
+// compile-time step index: one scalar bit test and branch per step, every step straight-line code) it calls rel() -- the
+// caller's workgroup barrier.  After it L(t, j) is final for every j <= 4 s + 3; the later steps store columns beyond that
+// only.  Every bit must be the index of a live step (0 .. (NC - 1) / 4): rel() never runs for another one, and the caller's
+// other waves, which count their barriers from the same mask, would wait for it.
 struct CholNoRelease { __device__ __forceinline__ void operator()() const { } };
 template <int NT, int JK, int C0, int OUT = 1, int NC = 0>
 struct CholPSteps {
     template <class RelFn>
     __device__ __forceinline__ static void run(d4 (&acc)[CholM<NT>::NTL], double *Lp, int n, double *colbuf, int lane, unsigned &bad,
-                                               int ksync, RelFn &rel)
+                                               unsigned relmask, RelFn &rel)
     {
         static_assert(OUT != 2 || (NC > 0 && NC <= 16 * NT), "the tile variant takes n as a template argument too");
         if constexpr (JK < NT) {
@@ -775,7 +777,7 @@ struct CholPSteps {
                     const int It = lane >> 4;
                     const unsigned trow = (unsigned)(size_t)(ldouble *)Lp + (It * (It + 1) / 2 * 256 + (lane & 15)) * 8;     // element (lane, 0) of tile (It, 0)
                     lds_store4_lane_ranges<k0, NC, (JK * 256 + C0 * 16) * 8>(trow, l);
-                    if (ksync == k0 / 4) rel();                   // (the caller retires the stores before its barrier)
+                    if (relmask & (1u << (k0 / 4))) rel();        // (the caller retires the stores before its barrier)
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
@@ -822,21 +824,21 @@ struct CholPSteps {
                 }
             }
             // (OUT == 2: a step all of whose columns are padding stores nothing -- its zeros are the fill's)
-            CholPSteps<NT, (C0 == 12 ? JK + 1 : JK), (C0 + 4) & 15, OUT, NC>::run(acc, Lp, n, colbuf, lane, bad, ksync, rel);
+            CholPSteps<NT, (C0 == 12 ? JK + 1 : JK), (C0 + 4) & 15, OUT, NC>::run(acc, Lp, n, colbuf, lane, bad, relmask, rel);
         }
     }
 };
 
 // factor the matrix held in `acc` (see cholm_load_t: TRANSPOSED tiles); wave-local, returns -1 or 0 (some pivot was not positive)
 // (OUT == 2: n = NC, and the caller has zero-filled the NT (NT + 1) / 2 tiles of Lp -- the columns are stored below the diagonal only)
-// (OUT == 2 with ksync >= 0: rel() runs once, behind the tile stores of step ksync -- see CholPSteps)
+// (OUT == 2 with relmask != 0: rel() runs behind the tile stores of every step whose bit is set -- see CholPSteps)
 template <int NT, int OUT = 1, int NC = 0, class RelFn = CholNoRelease>
-__device__ __forceinline__ int cholp_factor(d4 (&acc)[CholM<NT>::NTL], double *Lp, int n, double *colbuf, int lane, int ksync = -1,
+__device__ __forceinline__ int cholp_factor(d4 (&acc)[CholM<NT>::NTL], double *Lp, int n, double *colbuf, int lane, unsigned relmask = 0u,
                                             RelFn rel = RelFn())
 {
     static_assert(OUT == 2 || std::is_same<RelFn, CholNoRelease>::value, "only the tile variant releases columns early");
     unsigned bad = 0u;                          // the largest pivot_rank so far
-    CholPSteps<NT, 0, 0, OUT, NC>::run(acc, Lp, n, colbuf, lane, bad, ksync, rel);
+    CholPSteps<NT, 0, 0, OUT, NC>::run(acc, Lp, n, colbuf, lane, bad, relmask, rel);
     wave_sync();
     return pivot_rank_not_positive(bad) ? 0 : -1;
 }

@@ -65,6 +65,59 @@ __host__ __device__ __forceinline__ bool pivot_not_positive(unsigned hi, unsigne
 // tests/cpp/mean_stop_threshold.cpp checks it on the host.
 constexpr double MEAN_STOP_SQ = 0x1.19799812dea11p-40;
 
+// The release plan of the exact-shape Msckf update (slk_step_fast.hpp, phases 0 - 2): behind which steps of the first
+// factorisation (four columns each, NKS = (N + 3) / 4 of them) wave 0 meets the other three waves in a workgroup barrier, and
+// which wave evaluates h(X) of which feature in which of its two passes.  c0 .. c3 = the pose indices of the four features,
+// already clamped to 0 .. K.  Feature f reads the rows tp_f .. tp_f + 5 of the factor (tp = 0 for pose 0, 6 + 6 c otherwise)
+// at the columns j <= tp_f + 5, final behind step r_f = (tp_f + 5) >> 2; ksmax = max r_f; e0 .. e3 = the features ordered by
+// (r_f, f); FAST_HX_STEPS = 3: one h(X) takes about three late steps (profiles/README.md).
+//   STAGGERED, where r_e1 + FAST_HX_STEPS <= ksmax (and, with need_c, only where the plan has its release C: the early pair
+//   makes wave 0's steps between A and B slower, and without S under the last steps nothing pays for that -- A + B alone
+//   measured 1.3 % behind the single release at k = 8, 1.8 % at k = 4, profiles/README.md):
+//     A = r_e1          the waves 1 / 2 evaluate e0 / e1 (pass 0), wave 0 factors on;
+//     B = ksmax         the waves 1 / 2 evaluate e2 / e3 (pass 1); wave 0 takes no feature;
+//     C = ksmax + hc    only when hc > 0 and C <= NKS - 2: S (wave 1) and the prefix sums (wave 3) under the last steps.
+//   OTHERWISE one release at ksmax: wave w evaluates feature w (pass 0), feature 0 goes to wave 1 as pass 1 when
+//     ksmax + FAST_HX_STEPS < NKS, else to wave 0 behind its last step.
+// Every bit of the mask is a live step (cp <= K: ksmax <= NKS - 1) and A < B < C, so wave 0 meets popcount(mask) barriers inside
+// its factorisation and the other waves count the same from the flags: 1 + staggered + C.  Every wave computes the plan from
+// the same four loads, in scalar arithmetic (a five-exchange sorting network on the keys 4 r_f + f).
+// tests/cpp/release_plan.cpp checks it on the host for every pose tuple.
+struct FastReleasePlan {
+    unsigned mask;       // bit s: a barrier behind the tile stores of step s
+    unsigned word;       // bits 6 w + 3 p .. + 2: the feature of wave w's pass p (FAST_PLAN_NONE: none); bit 24: staggered; bit 25: C
+};
+constexpr int FAST_HX_STEPS = 3, FAST_PLAN_NONE = 7;
+__host__ __device__ __forceinline__ FastReleasePlan fast_release_plan(int c0, int c1, int c2, int c3, int K, int hc, bool need_c)
+{
+    const int nks = (12 + 6 * K + 3) >> 2;
+    auto key = [](int c, int f) { return ((((c ? 6 + 6 * c : 0) + 5) >> 2) << 2) | f; };
+    int k0 = key(c0, 0), k1 = key(c1, 1), k2 = key(c2, 2), k3 = key(c3, 3);
+    auto cx = [](int &a, int &b) { const int lo = a < b ? a : b, hi = a < b ? b : a; a = lo; b = hi; };
+    cx(k0, k1); cx(k2, k3); cx(k0, k2); cx(k1, k3); cx(k1, k2);
+    const int ra = k1 >> 2, ksmax = k3 >> 2;
+    const unsigned none = (unsigned)FAST_PLAN_NONE;
+    auto pack = [](unsigned w0p0, unsigned w0p1, unsigned w1p0, unsigned w1p1, unsigned w2p0, unsigned w2p1, unsigned w3p0, unsigned w3p1) {
+        return w0p0 | (w0p1 << 3) | (w1p0 << 6) | (w1p1 << 9) | (w2p0 << 12) | (w2p1 << 15) | (w3p0 << 18) | (w3p1 << 21);
+    };
+    FastReleasePlan p;
+    const int c = ksmax + hc;
+    const bool hasc = hc > 0 && c <= nks - 2;
+    if (ra + FAST_HX_STEPS <= ksmax && (hasc || !need_c)) {
+        p.mask = (1u << ra) | (1u << ksmax) | (hasc ? 1u << c : 0u);
+        p.word = pack(none, none, (unsigned)k0 & 3u, (unsigned)k2 & 3u, (unsigned)k1 & 3u, (unsigned)k3 & 3u, none, none) | (1u << 24) |
+                 (hasc ? 1u << 25 : 0u);
+    } else {
+        const bool second = ksmax + FAST_HX_STEPS < nks;
+        p.mask = 1u << ksmax;
+        p.word = pack(second ? none : 0u, none, 1u, second ? 0u : none, 2u, none, 3u, none);
+    }
+    return p;
+}
+__host__ __device__ __forceinline__ int fast_plan_feature(const FastReleasePlan &p, int wave, int pass) { return (int)((p.word >> (6 * wave + 3 * pass)) & 7u); }
+__host__ __device__ __forceinline__ bool fast_plan_staggered(const FastReleasePlan &p) { return (p.word >> 24) & 1u; }
+__host__ __device__ __forceinline__ bool fast_plan_has_c(const FastReleasePlan &p) { return (p.word >> 25) & 1u; }
+
 // x < bound for a double x that is +0, positive, +inf or a NaN of either sign, from its upper dword alone and as an UNSIGNED
 // compare: bound's lower dword must be zero (then the lower dword of x cannot decide), the positive doubles order as their
 // bit patterns do, and every NaN has an upper dword >= 0x7ff00000, above any finite bound's -- false, as x < bound is.  The

@@ -36,6 +36,17 @@
 #define SLK_FBAIL(code) return false
 #endif
 
+// steps between the release B of a staggered plan and the release C under which S and the prefix sums run (fast_release_plan,
+// slk_math.hpp; 0: no C, S stays behind the barrier that closes h(X)) -- chosen by A/B, profiles/README.md
+#ifndef SLK_RELEASE_HC
+#define SLK_RELEASE_HC 3
+#endif
+// 1: the staggered plan only where it has its release C (A + B alone is behind the single release); 0: wherever two features
+// are final three steps ahead of the last one
+#ifndef SLK_RELEASE_NEED_C
+#define SLK_RELEASE_NEED_C 1
+#endif
+
 namespace slk {
 
 // f(FastIdx<I>()) for I = B .. E - 1 while I <= last (wave-uniform, in a scalar register): nested ifs, one scalar compare
@@ -758,6 +769,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     // column, both wave-uniform and held in scalar registers.  S, the block bases of the prefix sums, delta = L b and the
     // k-blocks below the diagonal of the factor update stop there: what lies beyond multiplies exact zeros.
     int jmax = 0, ksmax, bad;
+    FastReleasePlan plan;
     // the factor: from msckf_chol_kernel's workspace, or (a.wsfail == nullptr) factored HERE by wave 0 -- cholp_factor, panel
     // by rows, straight into the tiles -- while the other waves fetch the small arrays (against the factor through the
     // workspace for every step: same step time, 0.74 x instead of 1.28 x the algorithmic bytes,
@@ -782,15 +794,28 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         const double tabv = fast_series_table[tid < 26 ? tid : 25];
         bad = here ? 0 : (a.wsfail[bidx] >= 0);
         bool ok = true;
+        int cps[4], cmax = 0;
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
             const double cf = mp[4 * f + 3];
-            ok = ok && (cf >= 0.0) && (cf <= (double)K);
-            const int cp = ok ? (int)cf : 0, tp = cp ? 6 + 6 * cp : 0;
-            jmax = (tp + 5 > jmax) ? tp + 5 : jmax;
+            const bool in = (cf >= 0.0) && (cf <= (double)K);
+            ok = ok && in;
+            cps[f] = __builtin_amdgcn_readfirstlane(in ? (int)cf : 0);   // (the clamp of h(X): plan and addresses from the same indices)
+            cmax = cps[f] > cmax ? cps[f] : cmax;
         }
-        jmax = __builtin_amdgcn_readfirstlane(jmax);
+        jmax = __builtin_amdgcn_readfirstlane((cmax ? 6 + 6 * cmax : 0) + 5);
         ksmax = jmax >> 2;
+        // the release plan (slk_math.hpp), the same in every wave: all of them count the same barriers.  The factor through the
+        // workspace has nothing to release: the single-release plan of its ksmax (every feature on the newest observed pose)
+        // keeps the second-pass rule, its mask is not used
+        bool single = !here;
+#ifdef SLK_STAMPS
+        single = single || a.stop == 3;                         // (a run that leaves at stamp 3: the waves 1 - 3 are gone behind the first release)
+#endif
+        plan = single ? fast_release_plan(cmax, cmax, cmax, cmax, K, 0, true)
+                      : fast_release_plan(cps[0], cps[1], cps[2], cps[3], K, SLK_RELEASE_HC, SLK_RELEASE_NEED_C != 0);
+        plan.mask = (unsigned)__builtin_amdgcn_readfirstlane((int)plan.mask);      // (two scalar registers: the mask dies with
+        plan.word = (unsigned)__builtin_amdgcn_readfirstlane((int)plan.word);      // wave 0's last step, the word with phase 2)
         bad |= !ok;
         if (tid < NSO3) bad |= !(pdg < 9.869604401089358);
         if (tid < Nq) mu[tid] = mu0;
@@ -817,22 +842,36 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
             }
             __syncthreads();
             // RELEASE: h(X) of a feature on pose c reads the rows tp .. tp + 5 of the factor at the columns j <= tp + 5 <= jmax,
-            // and step s of the factorisation leaves L(t, j) final for every j <= 4 s + 3.  Behind the tile stores of step ksmax
-            // (the step that holds column jmax; cp <= K, so it is one of the live steps 0 .. NKS - 1 and the barrier is always
-            // met) wave 0 meets the other three in one workgroup barrier and runs its remaining steps -- columns beyond jmax,
-            // which nothing reads before the barrier that closes phase 1 -- while they evaluate their features.  With the
-            // newest pose observed (ksmax = NKS - 1) the barrier stands at the end of the factorisation.
-            // colbuf = [oRef, oStr + 64): ref, delta, md32, d0, d0s, pd, cq, str -- all first written behind phase 1 (the union
-            // region, where it used to be, holds Yp, which the early h(X) writes)
+            // and step s of the factorisation leaves L(t, j) final for every j <= 4 s + 3.  Behind the tile stores of every step
+            // in plan.mask (fast_release_plan, slk_math.hpp: every bit a live step 0 .. NKS - 1, because cp <= K, so each barrier
+            // is always met) wave 0 meets the other three in a workgroup barrier and runs its remaining steps -- columns which
+            // nothing reads before the next release or the barrier that closes phase 1 -- while they work on what is final:
+            //   one bit, ksmax (the step that holds column jmax): every feature behind it; with the newest pose observed
+            //     (ksmax = NKS - 1) the barrier stands at the end of the factorisation;
+            //   staggered, A < B = ksmax [< C]: the two features that are final first behind A, the other two behind B, S and
+            //     the prefix sums (which read only what h(X) wrote) behind C.
+            // The other waves count their barriers from the plan's flags (phase 1), wave 0 from the mask: the same number.
+            // colbuf = [oRef, oStr + 64): ref, delta, md32, d0, d0s, pd, cq, str -- all first written behind phase 1.  The union
+            // region, where it used to be, holds what the released waves write while wave 0 factors on: Yp, dZ, innov, dz0 of
+            // the early h(X), tmpS and Sm of an early S.  The factorisation never touches that region.
             static_assert(CholM<NT>::COLBUF <= F::oStr + 64 - F::oRef, "colbuf fits the arrays of the gain phase and the mean loop");
             if (wave == 0) {
-                bad |= cholp_factor<NT, 2, N>(fa, Lt, N, ref, lane, ksmax, [&]() __attribute__((always_inline)) {
+#ifdef SLK_STAMPS
+                int nrel = 0;                                   // (stamps: wave 0 reaches / leaves the barriers A, B, C at 1 / 2, 9 / 10, 5 / 31)
+#endif
+                bad |= cholp_factor<NT, 2, N>(fa, Lt, N, ref, lane, plan.mask, [&]() __attribute__((always_inline)) {
                     wave_sync();                                // (the tile stores of this step and every one before it)
+#ifdef SLK_STAMPS
+                    SLK_WSTAMP(0, nrel == 0 ? 1 : (nrel == 1 ? 9 : 5));
+#endif
                     __builtin_amdgcn_s_barrier();
-                    SLK_WSTAMP(0, 16);
+#ifdef SLK_STAMPS
+                    SLK_WSTAMP(0, nrel == 0 ? 2 : (nrel == 1 ? 10 : 31));
+                    ++nrel;
+#endif
                 }) >= 0;
             } else {
-                __syncthreads();
+                __syncthreads();                                // (the first release: A, or the only one)
             }
         } else {
             __syncthreads();                                    // (the factor through the workspace: every wave stored its part of the tiles)
@@ -840,18 +879,26 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
     }
     SLK_FSTAMP(3);                                              // (thread 0: the end of the factorisation)
 
-    // ---- phase 1: Z = h(X) (Msckf.hpp:231-232), one wave per feature, lane j = the sigma pair of column j.  Waves 1 - 3 start
-    // behind the release above, wave 0 behind its last step; the filter may be one that is about to leave (failed
-    // factorisation, bad pose index, rotation bound -- decided in the barrier that closes this phase): the pose index is
-    // clamped before it forms an address, everything else h(X) reads lies at addresses that do not depend on data.
-    // Feature 0: with R = wave 0's steps behind the release and H = one h(X), wave 0 taking it ends the phase at R + H, wave 1
-    // taking it as a second pass at max(R, 2 H) -- ahead when R >= H.  H is about the time of three of the late steps
-    // (profiles/README.md), so the second pass runs when at least three steps follow the release (wave-uniform: ONE copy of
-    // the code, a uniform loop), else every wave has its own feature
-    const bool second = ksmax + 3 < NKS;
-    int f = wave;
-    for (bool go = wave != 0 || !second; go; go = second && f == 1, f = 0) {
-        if (f == wave) { SLK_WSTAMP(0, 17); SLK_WSTAMP(1, 19); }
+    // ---- phase 1: Z = h(X) (Msckf.hpp:231-232), one wave per feature and pass, lane j = the sigma pair of column j.  Waves
+    // 1 - 3 start behind the first release above, wave 0 behind its last step; the filter may be one that is about to leave
+    // (failed factorisation, bad pose index, rotation bound -- decided in the barrier that closes this phase): the pose index
+    // is clamped before it forms an address, everything else h(X) reads lies at addresses that do not depend on data.
+    // Which wave takes which feature in which pass is the plan's (fast_release_plan): the body writes Yp, dZ, innov and dz0 by
+    // FEATURE index, so the assignment changes no bit.  ONE copy of the code, a uniform loop over the two passes.
+    //   single release: every wave its own feature.  Feature 0: with R = wave 0's steps behind the release and H = one h(X),
+    //     wave 0 taking it ends the phase at R + H, wave 1 taking it as a second pass at max(R, 2 H) -- ahead when R >= H.  H is
+    //     about the time of three of the late steps (profiles/README.md), so the second pass runs when at least three steps
+    //     follow the release;
+    //   staggered: the waves 1 and 2 take the two features that are final first behind A and, behind one more barrier that
+    //     every wave but wave 0 meets here (wave 0: in its step B), the other two.  Wave 0 takes none.  A released wave that is
+    //     late makes wave 0 wait in its next release; nothing but time depends on the estimate H.
+    const bool staggered = fast_plan_staggered(plan);
+#pragma nounroll
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1 && staggered && wave != 0) __syncthreads();  // B
+        const int f = fast_plan_feature(plan, wave, pass);
+        if (f == FAST_PLAN_NONE) continue;
+        if (pass == 0) { SLK_WSTAMP(0, 17); SLK_WSTAMP(1, 19); }
         const double cf = mp[4 * f + 3];
         const int cp = (cf >= 0.0 && cf <= (double)K) ? (int)cf : 0;
         const int tp = cp ? 6 + 6 * cp : 0, sp = cp ? 6 + 7 * cp : 0;
@@ -900,17 +947,36 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         }
         SLK_WSTAMP(0, 18); SLK_WSTAMP(1, 21);
     }
-    // the barrier that closes phase 1 is the one in which the conditions of phase 0 meet: failed factorisation, bad index and
-    // rotation bound first, then the flag of h(X)'s exponential -- both before any global write
-    if (__syncthreads_or(bad)) SLK_FBAIL(2);
-    if (ints[50]) SLK_FBAIL(3);
-    // (the factorisation's colbuf is dead: the zeros these arrays start from; their first readers are phases away)
-    if (tid < 64) { str[tid] = 0.0; pd[tid] = 0.0; }
-    if (tid < 32) { d0[tid] = 0.0; md32[tid] = 0.0; }
-    SLK_FSTAMP(4);
-
-    // ---- phase 2: S = 1/2 sum (Z_i - mean_z)(Z_i - mean_z)^T + R (:238) on wave 1
+    // ---- phase 2: S = 1/2 sum (Z_i - mean_z)(Z_i - mean_z)^T + R (:238) on wave 1, the prefix sums of the factor update on
+    // wave 3: ONE copy of the code, with the barrier that closes phase 1 in front of it or behind it.  Both read only what h(X)
+    // wrote (Yp, dZ, dz0; R from memory), at addresses that do not depend on data, and write registers (wave 3) and tmpS / Sm in
+    // the union region, which the factorisation never touches.  So
+    //   with a release C in the plan (early_s) they run behind C, under wave 0's last steps and possibly on a filter that is
+    //     about to leave; the closing barrier follows and is also the barrier behind S -- it separates wave 1's reads of Yp
+    //     from wave 3's fast_prefix_park below;
+    //   without one the closing barrier comes first and S has a barrier of its own behind it, as before.
+    // (S in two places instead, each writing Gs / Gt: 128 VGPRs and 368 B of scratch at k = 8 -- the sums meet in fifty phis.)
+    // The barrier that closes phase 1 is the one in which the conditions of phase 0 meet: failed factorisation, bad index and
+    // rotation bound first, then the flag of h(X)'s exponential -- every bail-out before any global write, whatever ran early.
+    // The zeros of str / pd / d0 / md32 stay behind it: wave 0's colbuf lies on them until its last step.
+    // Gs and Gt live across the closing barrier when S is early (else across the barrier behind S, as before), and the park.
     double Gs[NKS - 1], Gt[36];                                 // wave 3: the factor update's prefix sums, block bases and tails
+    const bool early_s = fast_plan_has_c(plan);
+    // (the closing barrier with its bail-outs and zeros: two copies of a barrier and four stores, ONE of S and the prefix sums)
+    auto close_phase1 = [&]() __attribute__((always_inline)) {
+        if (__syncthreads_or(bad)) return 2;
+        if (ints[50]) return 3;
+        // (the factorisation's colbuf is dead: the zeros these arrays start from; their first readers are phases away)
+        if (tid < 64) { str[tid] = 0.0; pd[tid] = 0.0; }
+        if (tid < 32) { d0[tid] = 0.0; md32[tid] = 0.0; }
+        return 0;
+    };
+    if (!early_s) {
+        if (const int code = close_phase1()) SLK_FBAIL(code);
+        SLK_FSTAMP(4);
+    } else if (wave != 0) {
+        __syncthreads();                                        // C
+    }
     if (wave == 1) {
         d4 acc = {0.0, 0.0, 0.0, 0.0};
         fast_steps_to<0, NKS>(ksmax, [&](auto ix) __attribute__((always_inline)) {      // (the columns beyond jmax hold y+ = y- = 0)
@@ -924,6 +990,7 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         const double *R = a.R + (size_t)bidx * a.r_stride;
         const int row = lane & 7, col = lane >> 3;
         Sm[lane] = 0.5 * ((tmpS[lane] + tmpS[64 + lane]) - (double)S * dz0[row] * dz0[col]) + R[lane];
+        SLK_WSTAMP(1, 16);
     } else if (wave == 3) {
         // prefix sums over the columns of dZ dZ^T for the factor update (fast_prefix_blocks): the base of every block of four
         // columns from an MFMA chain beside S's, kept in registers -- no LDS is free before S is done.  On the wave that
@@ -932,7 +999,12 @@ __device__ __forceinline__ bool msckf_step_fast(const KArgs &a, double *smem)
         __builtin_amdgcn_sched_barrier(0);                      // (tails, then the chain: the neighbours' deviations are dead by then)
         fast_prefix_blocks<NKS>(dZi, c16, g4, Gs);              // (no stamp here: with one the stamps build spills 42 registers)
     }
-    __syncthreads();
+    if (early_s) {
+        if (const int code = close_phase1()) SLK_FBAIL(code);
+        SLK_FSTAMP(4);
+    } else {
+        __syncthreads();
+    }
     SLK_FSTAMP(6);
     // The block bases go to the Yp rows (dead: S is done), the first min(ksmax + 2, NKS) slots of [0, NKS * kPrefixSlot) of the
     // union (the slots behind them are neither written nor read), from the MFMA layout to lane = column: wave 3 alone writes
